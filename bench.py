@@ -1,6 +1,7 @@
 """bench.py - training images/s of the MI355X DeepLabv2/ResNet-101 MaxSquare UDA step.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torchrun)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                           (N > 1: launched by torchrun)
 
 A "step" is one iteration of tools/solve_gta5.py:335-387: one source image
 (fwd, CE, bwd) + one target image (fwd, MaxSquare, bwd) + the gradient
@@ -10,11 +11,25 @@ BASELINE.json configs[1]: GTA5->Cityscapes MaxSquare, 1024x512, bs=1/GPU,
 random-init (counter generator) weights, synthetic inputs already in HBM,
 --multi False, lambda_target 0.1, fp32.  Scaling is weak (bs=1 per GPU).
 
-Printed (rank 0, one JSON line): value = total images/s over all ranks, the
-roofline of the dominant kernel (layer3's dilated 3x3 forward, timed live with
-HIP events on its stream during the timed steps), the CPU baseline (the oracle's
-PyTorch-CPU restatement of the same step, a bounded sample on this host), and
-the relative loss delta of the first iteration vs that CPU reference.
+A plain run sets up, warms up, times the K steps and prints (rank 0) one JSON
+line: value = total images/s over all ranks, ms_per_step = the milliseconds one
+timed step took, and the step's conv FLOPs against the matrix-pipe bound
+(arithmetic on ms_per_step, no run of its own).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step left
+with its caller as DIR/<name>.npy (float32): the two loss scalars, three whole
+weight tensors and a fixed seeded sample of the model state (every parameter
+and BatchNorm running statistic after the step's SGD update).  Inputs and
+initial weights come from counter generators, so two runs with the same
+arguments start from identical data.
+
+--full adds the measurements that take runs of their own: the roofline of the
+dominant kernel (layer3's dilated 3x3 forward, timed with HIP events on its
+stream: during the timed steps of an eager run, on one extra eager iteration
+after the replays of a graphed one), the CPU baseline (the oracle's PyTorch-CPU
+restatement of the same step, a bounded sample on this host) and the relative
+loss delta of the first iteration vs that CPU reference.  Without --full these
+three fields are null.
 """
 import argparse
 import json
@@ -22,6 +37,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -103,10 +119,37 @@ def parse():
                     help="with --pair 0: the target forward runs on a side stream concurrently with the source backward")
     ap.add_argument("--async-wgrad", type=int, default=0,
                     help="1: in-place weight gradients on a side stream beside the data-gradient chain (ops.ASYNC_WGRAD)")
-    ap.add_argument("--cpu-baseline-iters", type=int, default=2, help="0 disables the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the dominant kernel (roofline) and run the CPU baseline / first-iteration loss "
+                         "check; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-baseline-iters", type=int, default=2, help="with --full; 0 disables the CPU baseline")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="PMC-derived HBM traffic per launch of the dominant kernel (from a rocprofv3 --pmc run)")
     return ap.parse_args()
+
+
+DUMP_WHOLE = ("conv1.weight", "layer3.5.conv2.weight", "layer6.conv2d_list.0.weight")
+DUMP_SAMPLE = 2 * 1024 * 1024  # elements of the model state kept by --dump-outputs (8 MB as float32)
+
+
+def dump_outputs(tr, outdir):
+    """What the last uda_step left with its caller, as float32 .npy files: the loss scalars, the weight
+    tensors named in DUMP_WHOLE, and DUMP_SAMPLE elements of the flattened floating-point model state (every
+    parameter and BatchNorm running statistic, in state_dict order) at indices drawn once from a seeded
+    generator, so two runs sample the same elements."""
+    os.makedirs(outdir, exist_ok=True)
+    torch.cuda.synchronize()
+    state = {k: v.detach() for k, v in tr.model.state_dict().items() if v.is_floating_point()}
+    out = {"loss_seg": tr.loss_val.detach(), "loss_target": tr.loss_target.detach()}
+    for k in DUMP_WHOLE:
+        out[k] = state[k]
+    flat = torch.cat([v.reshape(-1).float() for v in state.values()])
+    idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=min(DUMP_SAMPLE, flat.numel())))
+    out["state_sample"] = flat[torch.from_numpy(idx).to(flat.device)]
+    for k, v in out.items():
+        np.save(os.path.join(outdir, k + ".npy"), v.float().cpu().numpy())
 
 
 def main():
@@ -126,7 +169,8 @@ def main():
     ops.ASYNC_WGRAD = bool(a.async_wgrad)
     tr = UDATrainer(args, cuda=True)
     rank, dev = tr.rank, tr.device
-    init_state = {k: v.detach().cpu().clone() for k, v in tr.model.state_dict().items()} if rank == 0 else None
+    cpu_leg = a.full and world == 1 and a.cpu_baseline_iters > 0
+    init_state = {k: v.detach().cpu().clone() for k, v in tr.model.state_dict().items()} if cpu_leg else None
 
     # inputs resident in HBM before timing: two (source, label, target) triples per rank
     H, W, C = a.height, a.width, a.num_classes
@@ -144,10 +188,10 @@ def main():
     first_losses = None
     for i in range(max(a.warmup, 1 if graphed else 0)):
         tr.uda_step(*batches[i % 2])
-        if i == 0:
+        if i == 0 and cpu_leg:
             first_losses = {"loss_seg": tr.loss_val.detach().clone(), "loss_target": tr.loss_target.detach().clone()}
     torch.cuda.synchronize()
-    if not graphed:
+    if a.full and not graphed:
         ops.PROBE[key] = []
         if tr.overlap and not tr.pair:  # eager: time the probe's kernel on its own in one sequential iteration below
             ops.PROBE.pop(key)
@@ -162,7 +206,9 @@ def main():
     if dist.is_initialized():
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if graphed or key not in ops.PROBE:
+    if a.dump_outputs and rank == 0:
+        dump_outputs(tr, a.dump_outputs)
+    if a.full and (graphed or key not in ops.PROBE):
         # HIP events cannot time kernels inside a replayed graph: the dominant kernel is timed on
         # one eager iteration right after the timed replays (same shapes, the trained weights).
         # A spin kernel first keeps the GPU busy while the host enqueues that iteration (~35 ms of
@@ -175,8 +221,7 @@ def main():
         tr.overlap = False  # the probe times the kernel alone, not sharing the GPU with another stream
         tr._uda_body(*batches[0])
         torch.cuda.synchronize()
-    probes = ops.PROBE.pop(key)
-    kern_ms = sum(s.elapsed_time(e) for s, e in probes) / max(len(probes), 1)
+    probes = ops.PROBE.pop(key) if a.full else None
 
     el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if dist.is_initialized():
@@ -187,45 +232,12 @@ def main():
         dist.destroy_process_group()
         return
 
-    flops = 2.0 * 256 * 256 * 9 * h3 * w3 * nimg
-    achieved = flops / (kern_ms * 1e-3) / 1e12
     form = ops.f32_form() if a.conv_math == "fp32" else a.conv_math
-    # the op the probe timed: the stream-K GEMM + its piece-reduce launch
-    kernels = "k_igemm_fwd_sk,k_sk_reduce"
-    traffic, rec = None, None
-    if os.path.exists(a.pmc):
-        try:
-            rec = json.load(open(a.pmc))
-        except Exception:
-            rec = None
-    # the committed PMC figure counts only if it was measured on this very kernel: form, image count,
-    # map size and the launches one op call makes
-    if rec is not None and (rec.get("form") == form and rec.get("nimg") == nimg and rec.get("h") == h3
-                            and rec.get("w") == w3 and rec.get("kernel") == kernels):
-        traffic = rec.get("hbm_bytes_per_launch")
-    # the bound of the kernel's own arithmetic: FP32 MFMA, BF16 MFMA, or BF16 MFMA at six
-    # products per fp32 product (the bf16x6 form): 2500 / 6 = 416.7 fp32-equivalent TFLOP/s
-    # and FP16 MFMA (same rate) at three products per fp32 product (the f16x3 form): 833.3
-    peak = {"mfma_f32": FP32_MFMA_PEAK_TFLOPS, "bf16": BF16_MFMA_PEAK_TFLOPS, "fp16": BF16_MFMA_PEAK_TFLOPS,
-            "bf16x6": round(BF16_MFMA_PEAK_TFLOPS / 6, 1), "f16x3": round(BF16_MFMA_PEAK_TFLOPS / 3, 1)}[form]
-    roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4), "traffic": traffic,
-                "traffic_source": (os.path.relpath(a.pmc, ROOT) + ": committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                   "passes of this kernel (scripts/gpu_bench_prof.sh), not measured in this run; "
-                                   "memory-side bytes incl. Infinity-Cache hits") if traffic is not None else None,
-                "kernel": f"dconv3x3 fwd layer3 d=2 over {nimg} image(s): one op call = the stream-K GEMM "
-                          "k_igemm_fwd_sk(2) + its piece reduce k_sk_reduce (the weight planes are split at pack "
-                          "time, once per SGD step; f16x3: the input's absmax partials come from the BN kernel "
-                          "that produced it)",
-                "form": form, "kernel_ms": round(kern_ms, 4), "launches": len(probes),
-                "algorithmic_gflop_per_launch": round(flops / 1e9, 3),
-                # NOT a utilisation: fp32-equivalent TFLOP/s of the f16x3 / bf16x6 forms (3 / 6 MFMAs per
-                # fp32 product on the FP16 / BF16 pipes) compared with the FP32 matrix pipe's spec
-                "fp32_equiv_speedup_vs_fp32_mfma_spec": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4)}
+    roofline = kernel_roofline(a, probes, form, nimg, h3, w3) if a.full else None
 
     cpu = None
     loss_delta = None
-    if world == 1 and a.cpu_baseline_iters > 0:
+    if cpu_leg:
         from oracle import msl_oracle as orc
         nthreads = torch.get_num_threads()
         model = orc.Model(init_state, C)
@@ -280,6 +292,47 @@ def main():
     print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+def kernel_roofline(a, probes, form, nimg, h3, w3):
+    """The roofline record of the dominant kernel (--full) from the probe's HIP event pairs."""
+    kern_ms = sum(s.elapsed_time(e) for s, e in probes) / max(len(probes), 1)
+    flops = 2.0 * 256 * 256 * 9 * h3 * w3 * nimg
+    achieved = flops / (kern_ms * 1e-3) / 1e12
+    # the op the probe timed: the stream-K GEMM + its piece-reduce launch
+    kernels = "k_igemm_fwd_sk,k_sk_reduce"
+    traffic, rec = None, None
+    if os.path.exists(a.pmc):
+        try:
+            rec = json.load(open(a.pmc))
+        except Exception:
+            rec = None
+    # the committed PMC figure counts only if it was measured on this very kernel: form, image count,
+    # map size and the launches one op call makes
+    if rec is not None and (rec.get("form") == form and rec.get("nimg") == nimg and rec.get("h") == h3
+                            and rec.get("w") == w3 and rec.get("kernel") == kernels):
+        traffic = rec.get("hbm_bytes_per_launch")
+    # the bound of the kernel's own arithmetic: FP32 MFMA, BF16 MFMA, or BF16 MFMA at six
+    # products per fp32 product (the bf16x6 form): 2500 / 6 = 416.7 fp32-equivalent TFLOP/s
+    # and FP16 MFMA (same rate) at three products per fp32 product (the f16x3 form): 833.3
+    peak = {"mfma_f32": FP32_MFMA_PEAK_TFLOPS, "bf16": BF16_MFMA_PEAK_TFLOPS, "fp16": BF16_MFMA_PEAK_TFLOPS,
+            "bf16x6": round(BF16_MFMA_PEAK_TFLOPS / 6, 1), "f16x3": round(BF16_MFMA_PEAK_TFLOPS / 3, 1)}[form]
+    roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4), "traffic": traffic,
+                "traffic_source": (os.path.relpath(a.pmc, ROOT) + ": committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                                   "passes of this kernel (scripts/gpu_bench_prof.sh), not measured in this run; "
+                                   "memory-side bytes incl. Infinity-Cache hits") if traffic is not None else None,
+                "kernel": f"dconv3x3 fwd layer3 d=2 over {nimg} image(s): one op call = the stream-K GEMM "
+                          "k_igemm_fwd_sk(2) + its piece reduce k_sk_reduce (the weight planes are split at pack "
+                          "time, once per SGD step; f16x3: the input's absmax partials come from the BN kernel "
+                          "that produced it)",
+                "form": form, "kernel_ms": round(kern_ms, 4), "launches": len(probes),
+                "algorithmic_gflop_per_launch": round(flops / 1e9, 3),
+                # NOT a utilisation: fp32-equivalent TFLOP/s of the f16x3 / bf16x6 forms (3 / 6 MFMAs per
+                # fp32 product on the FP16 / BF16 pipes) compared with the FP32 matrix pipe's spec
+                "fp32_equiv_speedup_vs_fp32_mfma_spec": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4)}
+
+    return roofline
 
 
 if __name__ == "__main__":
