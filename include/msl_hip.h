@@ -396,6 +396,60 @@ int msl_multi_ce_up_bwd(const float* logits1, const float* logits2, int c, int h
 int msl_loss_labels_up(const float* logits1, const float* logits2, int c, int hi, int wi, int ho,
                        int wo, float thr, int32_t* argmax1, int32_t* label2, msl_stream_t stream);
 
+/* The MinEnt baseline, softCrossEntropy()(pred, softmax(pred)) (utils/loss.py:17-35,
+ * solve_gta5.py:151-152, :189): with lp = log_softmax(up(logits)) and p = softmax(up(logits)),
+ * out[0] = sum_px sum_c -lp_c p_c / (C*H*W).  The target softmax is not detached: the backward
+ * returns -p_c (lp_c + H) / (C*H*W), H the pixel's entropy. */
+int msl_entropy_up_fwd(const float* logits, int c, int hi, int wi, int ho, int wo, float* out,
+                       float* stats, void* ws, size_t ws_bytes, msl_stream_t stream);
+int msl_entropy_up_bwd(const float* logits, int c, int hi, int wi, int ho, int wo,
+                       const float* stats, const float* gout, float* dlogits, void* ws,
+                       size_t ws_bytes, msl_stream_t stream);
+
+/* IWsoftCrossEntropy(ratio)(pred, softmax(pred)) (utils/loss.py:37-67): hist = per-class count
+ * of the argmax of the upsampled LOGITS (first index on ties; int32, bit-exact), weights as
+ * msl_iw_maxsquare_up_fwd, out[0] = sum_px w[argmax] * sum_c -lp_c p_c / C.  hist/weights may
+ * be NULL. */
+int msl_iw_entropy_up_fwd(const float* logits, int c, int hi, int wi, int ho, int wo, float ratio,
+                          float* out, float* stats, int32_t* hist, float* weights, void* ws,
+                          size_t ws_bytes, msl_stream_t stream);
+int msl_iw_entropy_up_bwd(const float* logits, int c, int hi, int wi, int ho, int wo,
+                          const float* stats, const float* gout, float* dlogits, void* ws,
+                          size_t ws_bytes, msl_stream_t stream);
+
+/* The hard pseudo-label baseline (solve_gta5.py:149-150, :185-199): label = argmax p where
+ * max p > thr, else -1 (detached); out[0] = CE(up(logits), label), the mean over kept pixels
+ * (nan with a zero gradient if none, quirk Q8). */
+int msl_hard_ce_up_fwd(const float* logits, int c, int hi, int wi, int ho, int wo, float thr,
+                       float* out, float* stats, void* ws, size_t ws_bytes, msl_stream_t stream);
+int msl_hard_ce_up_bwd(const float* logits, int c, int hi, int wi, int ho, int wo, float thr,
+                       const float* stats, const float* gout, float* dlogits, void* ws,
+                       size_t ws_bytes, msl_stream_t stream);
+
+/* The decisions of the two kinds above, written out (int32 [ho*wo], either nullable): label =
+ * the hard pseudo-label (-1 = ignored), argmax_logits = the IW-entropy histogram's class. */
+int msl_pseudo_labels_up(const float* logits, int c, int hi, int wi, int ho, int wo, float thr,
+                         int32_t* label, int32_t* argmax_logits, msl_stream_t stream);
+
+/* softCrossEntropy / IWsoftCrossEntropy on explicit tensors, as the reference API takes them
+ * (loss.py:23, :46): inputs = hi-res logits [c][hw], target = a distribution [c][hw], elements
+ * equal to `ignore` masked out (m).  Plain: out[0] = the mean of -lp * target over the kept
+ * elements (nan with zero gradients if none); IW: out[0] = sum_px w[argmax inputs] * sum_c m *
+ * -lp_c target_c / c, hist / weights (nullable) as msl_iw_entropy_up_fwd.  The backward writes
+ * d inputs_c = a (p_c S - m_c t_c), S = sum_k m_k t_k, and d target = -a m lp (either nullable),
+ * a = gout / n (plain) or gout * w[argmax] / c (IW).  Workspace: msl_loss_workspace(c,1,1,1,hw). */
+int msl_soft_ce_fwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                    float* out, float* stats, void* ws, size_t ws_bytes, msl_stream_t stream);
+int msl_soft_ce_bwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                    const float* stats, const float* gout, float* dinputs, float* dtarget,
+                    msl_stream_t stream);
+int msl_iw_soft_ce_fwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                       float ratio, float* out, float* stats, int32_t* hist, float* weights,
+                       void* ws, size_t ws_bytes, msl_stream_t stream);
+int msl_iw_soft_ce_bwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                       const float* stats, const float* gout, float* dinputs, float* dtarget,
+                       msl_stream_t stream);
+
 /* Probability-input forms, for callers that hand the loss an explicit prob
  * tensor exactly as the reference API does (loss.py:76, :110).
  * prob is [c][hw]; label (nullable) is int64 [hw]. */

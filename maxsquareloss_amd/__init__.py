@@ -2,7 +2,7 @@
 
 Mirrors the reference's layout for the hot path only:
   graphs/models/deeplab_multi.py  - DeeplabMulti with HIP dilated convs / ASPP / upsample
-  utils/loss.py                   - MaxSquareloss, IW_MaxSquareloss, CrossEntropyLoss (fused HIP)
+  utils/loss.py                   - MaxSquareloss, IW_MaxSquareloss, softCrossEntropy, IWsoftCrossEntropy, CrossEntropyLoss (fused HIP)
   utils/optim.py                  - SGD with the reference's duplicated-parameter semantics
   utils/dist.py                   - bucketed RCCL all-reduce overlapped with the backward
   tools/solve_gta5.py, tools/train_source.py - the trainer entry points

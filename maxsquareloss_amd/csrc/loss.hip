@@ -6,6 +6,8 @@
 //   MaxSquareloss / IW_MaxSquareloss                   utils/loss.py:69-119
 //   nn.CrossEntropyLoss(ignore_index=-1)               train_source.py:128
 //   multi-level self-produced guidance label + CE      solve_gta5.py:206-213
+//   softCrossEntropy / IWsoftCrossEntropy (MinEnt)     utils/loss.py:17-67
+//   hard pseudo-label + CE (self-training)             solve_gta5.py:185-199
 //
 // The losses read the LOW-resolution logits [C][Hi][Wi] (0.6 MB, L2 resident)
 // and re-interpolate every hi-res pixel on the fly with torch-CPU's exact
@@ -26,7 +28,7 @@
 
 namespace msl {
 
-enum LossKind { K_CE = 0, K_MS = 1, K_IW = 2, K_MULTI = 3, K_UPS = 4 };
+enum LossKind { K_CE = 0, K_MS = 1, K_IW = 2, K_MULTI = 3, K_UPS = 4, K_ENT = 5, K_IWENT = 6, K_HARD = 7 };
 
 constexpr int kStats = 64;       // floats in a stats record
 constexpr int kFwdBlocks = 1024; // partial records per forward pass
@@ -129,6 +131,30 @@ __device__ __forceinline__ int multi_label(const float (&P)[CM], const float (&P
   return a;
 }
 
+// label of the hard target mode (solve_gta5.py:185-197): argmax p where max p > thr, else -1
+template <int CM>
+__device__ __forceinline__ int hard_label(const float (&p)[CM], int C, float thr) {
+  float best;
+  const int a = argmax_first<CM>(p, C, best);
+  return best > thr ? a : -1;
+}
+
+// log_softmax as (v_c - max) - log(sum) (never log(p_c): p_c may round to 0) and the pixel's
+// entropy H = sum_c (-lp_c) * p_c in ascending c, shared by the forward and the backward
+template <int CM>
+__device__ __forceinline__ float log_softmax_entropy(const float (&v)[CM], const float (&p)[CM],
+                                                     int C, float mx, float sum, float (&lp)[CM]) {
+  const float ls = logf(sum);
+  float h = 0.f;
+#pragma unroll
+  for (int c = 0; c < CM; ++c)
+    if (c < C) {
+      lp[c] = (v[c] - mx) - ls;
+      h += -lp[c] * p[c];
+    }
+  return h;
+}
+
 // Block-wide sum of one float (256 threads) -> returned to all threads.
 __device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);
@@ -143,6 +169,10 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 //   CE / MULTI: [0] = sum of -log p[y], [1] = n_valid
 //   MS:         [0] = sum p^2
 //   IW:         [0..C) = per-class sum of sum_k p_k^2 (by argmax class), [C..2C) = per-class count
+//   ENT:        [0] = sum of -lp * p (the pixel entropies)
+//   IWENT:      [0..C) = per-class sum of the pixel entropy (by the LOGITS' argmax class,
+//               loss.py:54), [C..2C) = per-class count
+//   HARD:       [0] = sum of -lp[y], [1] = n_valid (y = hard_label)
 template <int KIND, int CM>
 __global__ void __launch_bounds__(256) k_loss_fwd(const float* __restrict__ L1,
                                                    const float* __restrict__ L2,
@@ -201,10 +231,33 @@ __global__ void __launch_bounds__(256) k_loss_fwd(const float* __restrict__ L1,
         a0 += -((vy - mx) - logf(sum));
         a1 += 1.f;
       }
+    } else if (KIND == K_ENT) {
+      float lp[CM];
+      a0 += log_softmax_entropy<CM>(v, p, g.C, mx, sum, lp);
+    } else if (KIND == K_IWENT) {
+      float lp[CM], best;
+      const float h = log_softmax_entropy<CM>(v, p, g.C, mx, sum, lp);
+      const int am = argmax_first<CM>(v, g.C, best);
+#pragma unroll
+      for (int c = 0; c < CM; ++c)
+        if (c == am) {
+          cs[c] += h;
+          cn[c] += 1.f;
+        }
+    } else if (KIND == K_HARD) {
+      const int y = hard_label<CM>(p, g.C, thr);
+      if (y >= 0) {
+        float vy = v[0];
+#pragma unroll
+        for (int c = 1; c < CM; ++c)
+          if (c == y) vy = v[c];
+        a0 += -((vy - mx) - logf(sum));
+        a1 += 1.f;
+      }
     }
   }
   float* rp = part + (long long)blockIdx.x * rec;
-  if (KIND == K_IW) {
+  if (KIND == K_IW || KIND == K_IWENT) {
     for (int c = 0; c < g.C; ++c) {
       float s = 0.f, n = 0.f;
 #pragma unroll
@@ -231,7 +284,8 @@ __global__ void __launch_bounds__(256) k_loss_fwd(const float* __restrict__ L1,
 }
 
 // Deterministic finalize: one block sums the partial records in fixed order.
-// stats: [0] loss, [1] n_valid (CE/MULTI) or H*W (MS/IW), [2..2+C) class weights (IW)
+// stats: [0] loss, [1] n_valid (CE/MULTI/HARD) or H*W (MS/IW/ENT/IWENT), [2..2+C) class weights
+// (IW/IWENT)
 template <int KIND>
 __global__ void __launch_bounds__(256) k_loss_finalize(const float* __restrict__ part, int nblk,
                                                         int rec, int C, int npx, float ratio,
@@ -240,7 +294,7 @@ __global__ void __launch_bounds__(256) k_loss_finalize(const float* __restrict__
                                                         int32_t* __restrict__ hist,
                                                         float* __restrict__ weights) {
   __shared__ double sred[256];
-  const int nvals = KIND == K_IW ? 2 * C : 2;
+  const int nvals = (KIND == K_IW || KIND == K_IWENT) ? 2 * C : 2;
   __shared__ double vals[2 * kMaxC];
   for (int j = 0; j < nvals; ++j) {
     double s = 0.0;
@@ -256,7 +310,7 @@ __global__ void __launch_bounds__(256) k_loss_finalize(const float* __restrict__
   }
   if (threadIdx.x != 0) return;
   for (int k = 0; k < kStats; ++k) stats[k] = 0.f;
-  if (KIND == K_CE || KIND == K_MULTI) {
+  if (KIND == K_CE || KIND == K_MULTI || KIND == K_HARD) {
     const float n = (float)vals[1];
     const float loss = (float)(vals[0] / vals[1]);  // 0/0 -> nan, as the reference (quirk Q8)
     out[0] = loss;
@@ -267,8 +321,13 @@ __global__ void __launch_bounds__(256) k_loss_finalize(const float* __restrict__
     out[0] = loss;
     stats[0] = loss;
     stats[1] = (float)npx;
-  } else if (KIND == K_IW) {
-    // weight = 1 / max(hist^r * (sum hist)^(1-r), 1)   (loss.py:95), fp32 as the reference
+  } else if (KIND == K_ENT) {
+    const float loss = (float)(vals[0] / ((double)C * (double)npx));  // loss.py:33, no factor 1/2
+    out[0] = loss;
+    stats[0] = loss;
+    stats[1] = (float)npx;
+  } else if (KIND == K_IW || KIND == K_IWENT) {
+    // weight = 1 / max(hist^r * (sum hist)^(1-r), 1)   (loss.py:61, :95), fp32 as the reference
     float tot = 0.f;
     for (int c = 0; c < C; ++c) tot += (float)vals[C + c];
     const float tp = powf(tot, 1.f - ratio);
@@ -281,7 +340,7 @@ __global__ void __launch_bounds__(256) k_loss_finalize(const float* __restrict__
       if (hist) hist[c] = (int32_t)vals[C + c];
       l += (double)w * vals[c];
     }
-    const float loss = (float)(-l / (double)C);
+    const float loss = KIND == K_IW ? (float)(-l / (double)C) : (float)(l / (double)C);
     out[0] = loss;
     stats[0] = loss;
     stats[1] = (float)npx;
@@ -291,7 +350,7 @@ __global__ void __launch_bounds__(256) k_loss_finalize(const float* __restrict__
 // ---------------------------------------------------------------- backward
 // Per-pixel hi-res gradient g[c] = dL/d logit_hi[c] for the loss KIND.
 struct BwdScal {
-  float a;  // CE/MULTI: gout / n_valid ; MS: -gout / (C*H*W) ; IW: -2*gout / C
+  float a;  // CE/MULTI/HARD: gout / n_valid ; MS/ENT: -gout / (C*H*W) ; IW: -2*gout / C ; IWENT: -gout / C
 };
 
 template <int KIND, int CM>
@@ -311,11 +370,13 @@ __device__ __forceinline__ void pixel_grad(const float* __restrict__ L1, const f
   float v[CM], p[CM], mx, sum;
   up_logits<CM>(L1, g, ly, lx, v);
   softmax<CM>(v, g.C, p, mx, sum);
-  if (KIND == K_CE || KIND == K_MULTI) {
+  if (KIND == K_CE || KIND == K_MULTI || KIND == K_HARD) {
     int y;
     if (KIND == K_CE) {
       y = (int)labels[(long long)oy * g.Wo + ox];
       if (y >= g.C) y = -1;
+    } else if (KIND == K_HARD) {
+      y = hard_label<CM>(p, g.C, thr);
     } else {
       float v2[CM], P[CM], mx2, sum2;
       up_logits<CM>(L2, g, ly, lx, v2);
@@ -325,6 +386,23 @@ __device__ __forceinline__ void pixel_grad(const float* __restrict__ L1, const f
 #pragma unroll
     for (int c = 0; c < CM; ++c)
       if (c < g.C) gr[c] = y < 0 ? 0.f : sc * (p[c] - (c == y ? 1.f : 0.f));
+  } else if (KIND == K_ENT || KIND == K_IWENT) {
+    // d/dv_c sum_k -lp_k p_k = -p_c (lp_c + H): the target softmax is not detached (loss.py:33)
+    float lp[CM];
+    const float h = log_softmax_entropy<CM>(v, p, g.C, mx, sum, lp);
+    float a = sc;
+    if (KIND == K_IWENT) {
+      float best;
+      const int am = argmax_first<CM>(v, g.C, best);
+      float w = stats[2];
+#pragma unroll
+      for (int c = 1; c < CM; ++c)
+        if (c == am) w = stats[2 + c];
+      a = sc * w;
+    }
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < g.C) gr[c] = a * p[c] * (lp[c] + h);
   } else {
     float s2 = 0.f;
 #pragma unroll
@@ -385,9 +463,10 @@ __global__ void __launch_bounds__(256) k_bwd_rows(const float* __restrict__ L1,
   const int nw = ox_hi - ox_lo;  // <= wmax (host bound)
   const Lin ly = lin(oy, g.sh, g.Hi);
   float sc = 0.f;
-  if (KIND == K_CE || KIND == K_MULTI) sc = gout[0] / stats[1];
-  else if (KIND == K_MS) sc = -gout[0] / ((float)g.C * stats[1]);
+  if (KIND == K_CE || KIND == K_MULTI || KIND == K_HARD) sc = gout[0] / stats[1];
+  else if (KIND == K_MS || KIND == K_ENT) sc = -gout[0] / ((float)g.C * stats[1]);
   else if (KIND == K_IW) sc = -2.f * gout[0] / (float)g.C;
+  else if (KIND == K_IWENT) sc = -gout[0] / (float)g.C;
 
   for (int k = threadIdx.x; k < nw; k += 256) {
     const int ox = ox_lo + k;
@@ -575,6 +654,120 @@ __global__ void __launch_bounds__(256) k_prob_bwd(const float* __restrict__ prob
   }
 }
 
+// ---------------------------------------------------------------- soft cross-entropy, explicit tensors
+// softCrossEntropy / IWsoftCrossEntropy (loss.py:17-67) on hi-res logits x[C][hw] and an explicit
+// target distribution t[C][hw]; m = (t != ignore) per element.
+// record: plain: [0] = sum m * (-lp * t), [1] = sum m | IW: [0..C) per-class sums of the pixel's
+// sum_c m * (-lp * t) (by the logits' argmax class), [C..2C) class counts
+template <int CM>
+__device__ __forceinline__ void load_px(const float* __restrict__ x, int C, int hw, int px,
+                                        float (&v)[CM]) {
+#pragma unroll
+  for (int c = 0; c < CM; ++c)
+    if (c < C) v[c] = x[(long long)c * hw + px];
+}
+
+template <int IW, int CM>
+__global__ void __launch_bounds__(256) k_soft_fwd(const float* __restrict__ x,
+                                                   const float* __restrict__ t, int C, int hw,
+                                                   float ignore, float* __restrict__ part, int rec) {
+  __shared__ float red[4];
+  float a0 = 0.f, a1 = 0.f;
+  float cs[CM], cn[CM];
+#pragma unroll
+  for (int c = 0; c < CM; ++c) cs[c] = cn[c] = 0.f;
+  for (int px = blockIdx.x * 256 + threadIdx.x; px < hw; px += gridDim.x * 256) {
+    float v[CM], tt[CM], p[CM], mx, sum;
+    load_px<CM>(x, C, hw, px, v);
+    load_px<CM>(t, C, hw, px, tt);
+    softmax<CM>(v, C, p, mx, sum);
+    const float ls = logf(sum);
+    float s = 0.f, n = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < C && tt[c] != ignore) {
+        s += -((v[c] - mx) - ls) * tt[c];
+        n += 1.f;
+      }
+    if (!IW) {
+      a0 += s;
+      a1 += n;
+    } else {
+      float best;
+      const int am = argmax_first<CM>(v, C, best);
+#pragma unroll
+      for (int c = 0; c < CM; ++c)
+        if (c == am) {
+          cs[c] += s;
+          cn[c] += 1.f;
+        }
+    }
+  }
+  float* rp = part + (long long)blockIdx.x * rec;
+  if (IW) {
+    for (int c = 0; c < C; ++c) {
+      float s = 0.f, n = 0.f;
+#pragma unroll
+      for (int k = 0; k < CM; ++k)
+        if (k == c) {
+          s = cs[k];
+          n = cn[k];
+        }
+      s = block_sum(s, red);
+      n = block_sum(n, red);
+      if (threadIdx.x == 0) {
+        rp[c] = s;
+        rp[C + c] = n;
+      }
+    }
+  } else {
+    const float s0 = block_sum(a0, red);
+    const float s1 = block_sum(a1, red);
+    if (threadIdx.x == 0) {
+      rp[0] = s0;
+      rp[1] = s1;
+    }
+  }
+}
+
+// dx_c = a * (p_c * S - m_c t_c), S = sum_k m_k t_k; dt_c = -a * m_c * lp_c; a = gout / n (plain;
+// 0 when no element is kept: the reference's mean over nothing has a zero gradient) or
+// gout * w[argmax x] / C (IW).  dx / dt nullable.
+template <int IW, int CM>
+__global__ void __launch_bounds__(256) k_soft_bwd(const float* __restrict__ x,
+                                                   const float* __restrict__ t, int C, int hw,
+                                                   float ignore, const float* __restrict__ stats,
+                                                   const float* __restrict__ gout,
+                                                   float* __restrict__ dx, float* __restrict__ dt) {
+  const float g = gout[0];
+  for (int px = blockIdx.x * 256 + threadIdx.x; px < hw; px += gridDim.x * 256) {
+    float v[CM], tt[CM], p[CM], mx, sum;
+    load_px<CM>(x, C, hw, px, v);
+    load_px<CM>(t, C, hw, px, tt);
+    softmax<CM>(v, C, p, mx, sum);
+    const float ls = logf(sum);
+    float a;
+    if (IW) {
+      float best;
+      const int am = argmax_first<CM>(v, C, best);
+      a = g * stats[2 + am] / (float)C;
+    } else {
+      a = stats[1] > 0.f ? g / stats[1] : 0.f;
+    }
+    float S = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < C && tt[c] != ignore) S += tt[c];
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < C) {
+        const bool m = tt[c] != ignore;
+        if (dx) dx[(long long)c * hw + px] = a * (p[c] * S - (m ? tt[c] : 0.f));
+        if (dt) dt[(long long)c * hw + px] = m ? -a * ((v[c] - mx) - ls) : 0.f;
+      }
+  }
+}
+
 // ---------------------------------------------------------------- label inspection
 // The per-pixel decisions the fused losses take internally, written out: arg[px] = first-max
 // argmax of softmax(up(L1)) (the IW histogram's class, loss.py:84-86), label2[px] = the
@@ -601,6 +794,31 @@ __global__ void __launch_bounds__(256) k_loss_labels(const float* __restrict__ L
       up_logits<CM>(L2, g, ly, lx, v2);
       softmax<CM>(v2, g.C, P, mx2, sum2);
       label2[px] = multi_label<CM>(P, p, g.C, thr);
+    }
+  }
+}
+
+// The decisions of the hard / IW-entropy kinds: label[px] = hard_label of softmax(up(L1)) (-1 =
+// ignored), arg[px] = first-max argmax of the upsampled LOGITS (IWsoftCrossEntropy's histogram
+// class, loss.py:54).  Same device functions as k_loss_fwd / pixel_grad.
+template <int CM>
+__global__ void __launch_bounds__(256) k_pseudo_labels(const float* __restrict__ L1, Geo g,
+                                                        float thr, int32_t* __restrict__ label,
+                                                        int32_t* __restrict__ arg) {
+  const int npx = g.Ho * g.Wo;
+  for (int px = blockIdx.x * 256 + threadIdx.x; px < npx; px += gridDim.x * 256) {
+    const int oy = px / g.Wo, ox = px - oy * g.Wo;
+    const Lin ly = lin(oy, g.sh, g.Hi), lx = lin(ox, g.sw, g.Wi);
+    float v[CM];
+    up_logits<CM>(L1, g, ly, lx, v);
+    if (arg) {
+      float best;
+      arg[px] = argmax_first<CM>(v, g.C, best);
+    }
+    if (label) {
+      float p[CM], mx, sum;
+      softmax<CM>(v, g.C, p, mx, sum);
+      label[px] = hard_label<CM>(p, g.C, thr);
     }
   }
 }
@@ -703,6 +921,41 @@ static int loss_bwd(const float* L1, const float* L2, const int64_t* labels, con
   const int n = c * hi * wi;
   MSL_LAUNCH(k_bwd_cols, dim3(std::min(cdiv(n, 256), 2048)), dim3(256), 0, st,
                      (const float*)T, g, dlow);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+template <int IW>
+static int soft_fwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                    float ratio, float* out, float* stats, int32_t* hist, float* weights,
+                    void* ws, size_t ws_bytes, msl_stream_t stream) {
+  if (!inputs || !target || !out || !stats || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
+  if (ws_bytes < part_bytes(c)) return MSL_ERR_WORKSPACE;
+  hipStream_t st = as_stream(stream);
+  const int nblk = std::min(kFwdBlocks, cdiv(hw, 256));
+  const int rec = rec_len(c);
+  float* part = (float*)ws;
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_soft_fwd<IW, CM>), dim3(nblk), dim3(256), 0, st, inputs, target,
+                                    c, hw, ignore, part, rec));
+  MSL_CHECK_LAUNCH();
+  // plain: sum / count, nan when nothing is kept (the CE finalize); IW: sum_c w_c * sums_c / C
+  MSL_LAUNCH((k_loss_finalize<IW ? K_IWENT : K_CE>), dim3(1), dim3(256), 0, st,
+                     (const float*)part, nblk, rec, c, hw, ratio, out, stats, hist, weights);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+template <int IW>
+static int soft_bwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                    const float* stats, const float* gout, float* dinputs, float* dtarget,
+                    msl_stream_t stream) {
+  if (!inputs || !target || !stats || !gout || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
+  if (!dinputs && !dtarget) return MSL_OK;
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_soft_bwd<IW, CM>), dim3(std::min(cdiv(hw, 256), 4096)),
+                                    dim3(256), 0, as_stream(stream), inputs, target, c, hw,
+                                    ignore, stats, gout, dinputs, dtarget));
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }
@@ -815,6 +1068,88 @@ int msl_loss_labels_up(const float* logits1, const float* logits2, int c, int hi
                                     logits1, logits2, g, thr, argmax1, label2));
   MSL_CHECK_LAUNCH();
   return MSL_OK;
+}
+
+int msl_entropy_up_fwd(const float* logits, int c, int hi, int wi, int ho, int wo, float* out,
+                       float* stats, void* ws, size_t ws_bytes, msl_stream_t stream) {
+  return loss_fwd<K_ENT>(logits, nullptr, nullptr, c, hi, wi, ho, wo, 0.f, 0.f, out, stats,
+                         nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+int msl_entropy_up_bwd(const float* logits, int c, int hi, int wi, int ho, int wo,
+                       const float* stats, const float* gout, float* dlogits, void* ws,
+                       size_t ws_bytes, msl_stream_t stream) {
+  if (!logits || !stats || !gout) return MSL_ERR_ARG;
+  return loss_bwd<K_ENT>(logits, nullptr, nullptr, nullptr, c, hi, wi, ho, wo, 0.f, stats, gout,
+                         dlogits, ws, ws_bytes, stream);
+}
+
+int msl_iw_entropy_up_fwd(const float* logits, int c, int hi, int wi, int ho, int wo, float ratio,
+                          float* out, float* stats, int32_t* hist, float* weights, void* ws,
+                          size_t ws_bytes, msl_stream_t stream) {
+  return loss_fwd<K_IWENT>(logits, nullptr, nullptr, c, hi, wi, ho, wo, 0.f, ratio, out, stats,
+                           hist, weights, ws, ws_bytes, stream);
+}
+
+int msl_iw_entropy_up_bwd(const float* logits, int c, int hi, int wi, int ho, int wo,
+                          const float* stats, const float* gout, float* dlogits, void* ws,
+                          size_t ws_bytes, msl_stream_t stream) {
+  if (!logits || !stats || !gout) return MSL_ERR_ARG;
+  return loss_bwd<K_IWENT>(logits, nullptr, nullptr, nullptr, c, hi, wi, ho, wo, 0.f, stats,
+                           gout, dlogits, ws, ws_bytes, stream);
+}
+
+int msl_hard_ce_up_fwd(const float* logits, int c, int hi, int wi, int ho, int wo, float thr,
+                       float* out, float* stats, void* ws, size_t ws_bytes,
+                       msl_stream_t stream) {
+  return loss_fwd<K_HARD>(logits, nullptr, nullptr, c, hi, wi, ho, wo, thr, 0.f, out, stats,
+                          nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+int msl_hard_ce_up_bwd(const float* logits, int c, int hi, int wi, int ho, int wo, float thr,
+                       const float* stats, const float* gout, float* dlogits, void* ws,
+                       size_t ws_bytes, msl_stream_t stream) {
+  if (!logits || !stats || !gout) return MSL_ERR_ARG;
+  return loss_bwd<K_HARD>(logits, nullptr, nullptr, nullptr, c, hi, wi, ho, wo, thr, stats, gout,
+                          dlogits, ws, ws_bytes, stream);
+}
+
+int msl_pseudo_labels_up(const float* logits, int c, int hi, int wi, int ho, int wo, float thr,
+                         int32_t* label, int32_t* argmax_logits, msl_stream_t stream) {
+  if (!geo_ok(c, hi, wi, ho, wo) || !logits) return MSL_ERR_ARG;
+  if (!label && !argmax_logits) return MSL_OK;
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  const int nblk = std::min(4096, cdiv((long long)ho * wo, 256));
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_pseudo_labels<CM>), dim3(nblk), dim3(256), 0, as_stream(stream),
+                                    logits, g, thr, label, argmax_logits));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_soft_ce_fwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                    float* out, float* stats, void* ws, size_t ws_bytes, msl_stream_t stream) {
+  return soft_fwd<0>(inputs, target, c, hw, ignore, 0.f, out, stats, nullptr, nullptr, ws,
+                     ws_bytes, stream);
+}
+
+int msl_soft_ce_bwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                    const float* stats, const float* gout, float* dinputs, float* dtarget,
+                    msl_stream_t stream) {
+  return soft_bwd<0>(inputs, target, c, hw, ignore, stats, gout, dinputs, dtarget, stream);
+}
+
+int msl_iw_soft_ce_fwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                       float ratio, float* out, float* stats, int32_t* hist, float* weights,
+                       void* ws, size_t ws_bytes, msl_stream_t stream) {
+  return soft_fwd<1>(inputs, target, c, hw, ignore, ratio, out, stats, hist, weights, ws,
+                     ws_bytes, stream);
+}
+
+int msl_iw_soft_ce_bwd(const float* inputs, const float* target, int c, int hw, float ignore,
+                       const float* stats, const float* gout, float* dinputs, float* dtarget,
+                       msl_stream_t stream) {
+  return soft_bwd<1>(inputs, target, c, hw, ignore, stats, gout, dinputs, dtarget, stream);
 }
 
 int msl_maxsquare_prob_fwd(const float* prob, int c, int hw, float* out, void* ws,

@@ -76,6 +76,17 @@ SIGNATURES = {
     "msl_multi_ce_up_fwd": (c_int, [c_p, c_p] + [c_int] * 5 + [c_f, c_p, c_p, c_p, c_sz, c_p]),
     "msl_multi_ce_up_bwd": (c_int, [c_p, c_p] + [c_int] * 5 + [c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "msl_loss_labels_up": (c_int, [c_p, c_p] + [c_int] * 5 + [c_f, c_p, c_p, c_p]),
+    "msl_entropy_up_fwd": (c_int, [c_p] + [c_int] * 5 + [c_p, c_p, c_p, c_sz, c_p]),
+    "msl_entropy_up_bwd": (c_int, [c_p] + [c_int] * 5 + [c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_iw_entropy_up_fwd": (c_int, [c_p] + [c_int] * 5 + [c_f, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_iw_entropy_up_bwd": (c_int, [c_p] + [c_int] * 5 + [c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_hard_ce_up_fwd": (c_int, [c_p] + [c_int] * 5 + [c_f, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_hard_ce_up_bwd": (c_int, [c_p] + [c_int] * 5 + [c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_pseudo_labels_up": (c_int, [c_p] + [c_int] * 5 + [c_f, c_p, c_p, c_p]),
+    "msl_soft_ce_fwd": (c_int, [c_p, c_p, c_int, c_int, c_f, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_soft_ce_bwd": (c_int, [c_p, c_p, c_int, c_int, c_f, c_p, c_p, c_p, c_p, c_p]),
+    "msl_iw_soft_ce_fwd": (c_int, [c_p, c_p, c_int, c_int, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_iw_soft_ce_bwd": (c_int, [c_p, c_p, c_int, c_int, c_f, c_p, c_p, c_p, c_p, c_p]),
     "msl_maxsquare_prob_fwd": (c_int, [c_p, c_int, c_int, c_p, c_p, c_sz, c_p]),
     "msl_maxsquare_prob_bwd": (c_int, [c_p, c_int, c_int, c_p, c_p, c_p]),
     "msl_iw_maxsquare_prob_fwd": (c_int, [c_p, c_p, c_int, c_int, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),

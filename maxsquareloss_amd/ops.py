@@ -1107,6 +1107,104 @@ class _MultiCEUp(Function):
         return d, None, None, None, None
 
 
+class _EntropyUp(Function):
+    @staticmethod
+    def forward(ctx, low, ho, wo):
+        low = _check_act(low, "entropy_up")
+        c, hi, wi, ho, wo = _geom(low, (ho, wo))
+        lib = hip.load()
+        out = torch.empty((), dtype=_f32, device=low.device)
+        st = _stats(low.device)
+        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+        ws = hip.workspace(wsb, low.device)
+        hip.check(lib.msl_entropy_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, out.data_ptr(), st.data_ptr(),
+                                         ws.data_ptr(), wsb, hip.stream_ptr()), "msl_entropy_up_fwd")
+        ctx.save_for_backward(low, st)
+        ctx.geo = (c, hi, wi, ho, wo)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        low, st = ctx.saved_tensors
+        c, hi, wi, ho, wo = ctx.geo
+        lib = hip.load()
+        g = g.to(_f32).contiguous()
+        d = torch.empty_like(low)
+        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+        ws = hip.workspace(wsb, low.device)
+        hip.check(lib.msl_entropy_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, st.data_ptr(), g.data_ptr(),
+                                         d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
+                  "msl_entropy_up_bwd")
+        return d, None, None
+
+
+class _IWEntropyUp(Function):
+    @staticmethod
+    def forward(ctx, low, ho, wo, ratio):
+        low = _check_act(low, "iw_entropy_up")
+        c, hi, wi, ho, wo = _geom(low, (ho, wo))
+        lib = hip.load()
+        out = torch.empty((), dtype=_f32, device=low.device)
+        st = _stats(low.device)
+        hist = torch.empty(c, dtype=torch.int32, device=low.device)
+        weights = torch.empty(c, dtype=_f32, device=low.device)
+        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+        ws = hip.workspace(wsb, low.device)
+        hip.check(lib.msl_iw_entropy_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, float(ratio), out.data_ptr(),
+                                            st.data_ptr(), hist.data_ptr(), weights.data_ptr(), ws.data_ptr(),
+                                            wsb, hip.stream_ptr()), "msl_iw_entropy_up_fwd")
+        ctx.save_for_backward(low, st)
+        ctx.geo = (c, hi, wi, ho, wo)
+        ctx.mark_non_differentiable(hist, weights)
+        return out, hist, weights
+
+    @staticmethod
+    def backward(ctx, g, _gh, _gw):
+        low, st = ctx.saved_tensors
+        c, hi, wi, ho, wo = ctx.geo
+        lib = hip.load()
+        g = g.to(_f32).contiguous()
+        d = torch.empty_like(low)
+        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+        ws = hip.workspace(wsb, low.device)
+        hip.check(lib.msl_iw_entropy_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, st.data_ptr(), g.data_ptr(),
+                                            d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
+                  "msl_iw_entropy_up_bwd")
+        return d, None, None, None
+
+
+class _HardCEUp(Function):
+    @staticmethod
+    def forward(ctx, low, ho, wo, thr):
+        low = _check_act(low, "hard_ce_up")
+        c, hi, wi, ho, wo = _geom(low, (ho, wo))
+        lib = hip.load()
+        out = torch.empty((), dtype=_f32, device=low.device)
+        st = _stats(low.device)
+        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+        ws = hip.workspace(wsb, low.device)
+        hip.check(lib.msl_hard_ce_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, float(thr), out.data_ptr(),
+                                         st.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
+                  "msl_hard_ce_up_fwd")
+        ctx.save_for_backward(low, st)
+        ctx.geo = (c, hi, wi, ho, wo, float(thr))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        low, st = ctx.saved_tensors
+        c, hi, wi, ho, wo, thr = ctx.geo
+        lib = hip.load()
+        g = g.to(_f32).contiguous()
+        d = torch.empty_like(low)
+        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+        ws = hip.workspace(wsb, low.device)
+        hip.check(lib.msl_hard_ce_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, thr, st.data_ptr(), g.data_ptr(),
+                                         d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
+                  "msl_hard_ce_up_bwd")
+        return d, None, None, None
+
+
 def low_of(pred):
     """The low-resolution logits behind an upsampled prediction, or None when there are none or
     when either tensor was modified in place since the upsample (then the loss must read `pred`
@@ -1151,6 +1249,99 @@ def iw_maxsquare_up(low, out_hw, ratio):
 
 def multi_ce_up(low1, low2, out_hw, thr):
     return _MultiCEUp.apply(low1, low2, int(out_hw[0]), int(out_hw[1]), float(thr))
+
+
+def entropy_up(low, out_hw):
+    """softCrossEntropy()(pred, softmax(pred)) of the upsampled logits (loss.py:17-35): the mean over
+    C*H*W of -log_softmax * softmax, the gradient through both factors."""
+    return _EntropyUp.apply(low, int(out_hw[0]), int(out_hw[1]))
+
+
+def iw_entropy_up(low, out_hw, ratio):
+    """IWsoftCrossEntropy(ratio)(pred, softmax(pred)) (loss.py:37-67).  Returns (loss, hist int32[C] of
+    the logits' argmax, weights fp32[C])."""
+    return _IWEntropyUp.apply(low, int(out_hw[0]), int(out_hw[1]), float(ratio))
+
+
+def hard_ce_up(low, out_hw, thr):
+    """CE(pred, label) with the pseudo-label argmax p where max p > thr, else ignored
+    (solve_gta5.py:185-199); nan with a zero gradient when no pixel passes."""
+    return _HardCEUp.apply(low, int(out_hw[0]), int(out_hw[1]), float(thr))
+
+
+def _pseudo(low, out_hw, thr, want_label, want_arg):
+    low = _check_act(low.detach(), "pseudo_labels_up")
+    c, hi, wi, ho, wo = _geom(low, out_hw)
+    lab = torch.empty(ho * wo, dtype=torch.int32, device=low.device) if want_label else None
+    arg = torch.empty(ho * wo, dtype=torch.int32, device=low.device) if want_arg else None
+    hip.check(hip.load().msl_pseudo_labels_up(low.data_ptr(), c, hi, wi, ho, wo, float(thr), hip.ptr(lab),
+                                              hip.ptr(arg), hip.stream_ptr()), "msl_pseudo_labels_up")
+    return lab, arg
+
+
+def pseudo_labels_up(low, out_hw, thr):
+    """int32 [ho*wo]: the pseudo-label hard_ce_up trains on (-1 = ignored)."""
+    return _pseudo(low, out_hw, thr, True, False)[0]
+
+
+def logits_argmax_up(low, out_hw):
+    """int32 [ho*wo]: the first-max argmax of the upsampled logits (iw_entropy_up's histogram class)."""
+    return _pseudo(low, out_hw, 0.0, False, True)[1]
+
+
+# --------------------------------------------------------------------------- soft cross-entropy, explicit target
+class _SoftCE(Function):
+    """softCrossEntropy (ratio None) / IWsoftCrossEntropy on (1,C,H,W) logits and an explicit target."""
+
+    @staticmethod
+    def forward(ctx, inputs, target, ignore, ratio):
+        inputs = _check_act(inputs, "soft_ce")
+        target = _check_act(target, "soft_ce")
+        if inputs.shape != target.shape:
+            raise hip.MSLError(f"soft_ce: inputs {tuple(inputs.shape)} and target {tuple(target.shape)} differ")
+        c, hw = inputs.size(1), inputs.size(2) * inputs.size(3)
+        lib = hip.load()
+        out = torch.empty((), dtype=_f32, device=inputs.device)
+        st = _stats(inputs.device)
+        wsb = lib.msl_loss_workspace(c, 1, 1, 1, hw)
+        ws = hip.workspace(wsb, inputs.device)
+        ctx.save_for_backward(inputs, target, st)
+        ctx.meta = (c, hw, float(ignore), ratio is not None)
+        if ratio is None:
+            hip.check(lib.msl_soft_ce_fwd(inputs.data_ptr(), target.data_ptr(), c, hw, float(ignore), out.data_ptr(),
+                                          st.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()), "msl_soft_ce_fwd")
+            return out
+        hist = torch.empty(c, dtype=torch.int32, device=inputs.device)
+        weights = torch.empty(c, dtype=_f32, device=inputs.device)
+        hip.check(lib.msl_iw_soft_ce_fwd(inputs.data_ptr(), target.data_ptr(), c, hw, float(ignore), float(ratio),
+                                         out.data_ptr(), st.data_ptr(), hist.data_ptr(), weights.data_ptr(),
+                                         ws.data_ptr(), wsb, hip.stream_ptr()), "msl_iw_soft_ce_fwd")
+        ctx.mark_non_differentiable(hist, weights)
+        return out, hist, weights
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        inputs, target, st = ctx.saved_tensors
+        c, hw, ignore, iw = ctx.meta
+        g = g.to(_f32).contiguous()
+        di = torch.empty_like(inputs) if ctx.needs_input_grad[0] else None
+        dt = torch.empty_like(target) if ctx.needs_input_grad[1] else None
+        lib = hip.load()
+        fn = lib.msl_iw_soft_ce_bwd if iw else lib.msl_soft_ce_bwd
+        hip.check(fn(inputs.data_ptr(), target.data_ptr(), c, hw, ignore, st.data_ptr(), g.data_ptr(), hip.ptr(di),
+                     hip.ptr(dt), hip.stream_ptr()), "msl_soft_ce_bwd")
+        return di, dt, None, None
+
+
+def soft_ce(inputs, target, ignore_index=-1):
+    """softCrossEntropy(ignore_index)(inputs, target) (loss.py:17-35): the mean of -log_softmax(inputs) *
+    target over the elements with target != ignore_index; gradients to both."""
+    return _SoftCE.apply(inputs, target, float(ignore_index), None)
+
+
+def iw_soft_ce(inputs, target, ratio, ignore_index=-1):
+    """IWsoftCrossEntropy (loss.py:37-67) on explicit tensors.  Returns (loss, hist, weights)."""
+    return _SoftCE.apply(inputs, target, float(ignore_index), float(ratio))
 
 
 # --------------------------------------------------------------------------- prob-input losses

@@ -3,7 +3,8 @@
 One iteration (solve_gta5.py:335-387), with the same method names:
     poly_lr_scheduler
     pred = model(x_src);  train_source(pred, y)   # CE(x2,y) [+ lambda_seg*CE(x1,y)]; backward
-    pred = model(x_tgt);  train_target(pred)      # lambda_t*MaxSquare|IW-MaxSquare(x2)
+    pred = model(x_tgt);  train_target(pred)      # lambda_t*target_loss(x2), --target_mode: MaxSquare |
+                                                  # IW-MaxSquare | entropy | IW-entropy | hard pseudo-label CE
                                                   # [+ lambda_seg*lambda_t*CE(x1, label_2)]; backward
     optimizer.step(); optimizer.zero_grad()
 Gradients of the two backward passes accumulate; with WORLD_SIZE > 1 the
@@ -26,7 +27,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..utils.loss import IW_MaxSquareloss, MaxSquareloss, multi_level_guidance_ce
+from ..utils.loss import (IW_MaxSquareloss, IWsoftCrossEntropy, MaxSquareloss, multi_level_guidance_ce,
+                          pseudo_label_ce, softCrossEntropy)
 from ..utils.graph import GraphedStep
 from ..utils.synthetic import SyntheticDomain
 from .train_source import Trainer, add_train_args, init_args, str2bool
@@ -48,9 +50,16 @@ class UDATrainer(Trainer):
         elif mode == "IW_maxsquare":
             self.target_loss = IW_MaxSquareloss(ignore_index=-1, num_class=self.args.num_classes,
                                                 ratio=self.args.IW_ratio)
+        elif mode == "entropy":
+            self.target_loss = softCrossEntropy(ignore_index=-1)
+        elif mode == "IW_entropy":
+            self.target_loss = IWsoftCrossEntropy(ignore_index=-1, num_class=self.args.num_classes,
+                                                  ratio=self.args.IW_ratio)
+        elif mode == "hard":
+            # solve_gta5.py:149-150, :185-197: CE on the thresholded argmax label (utils/loss.py pseudo_label_ce)
+            self.target_loss = lambda pred: pseudo_label_ce(pred, self.threshold)
         else:
-            raise NotImplementedError(f"target_mode {mode!r} is outside the MI355X hot path "
-                                      "(maxsquare, IW_maxsquare)")
+            raise NotImplementedError(f"unknown target_mode {mode!r}")
         self.current_round = self.args.init_round
         self.round_num = self.args.round_num
         self.threshold = self.args.threshold
@@ -89,8 +98,9 @@ class UDATrainer(Trainer):
         return loss_
 
     def target_loss_total(self, pred):
-        """The target objective of solve_gta5.py:178-218 (maxsquare / IW_maxsquare target modes; meters
-        updated), without its backward."""
+        """The target objective of solve_gta5.py:178-218 (every target mode: the loss modules take the
+        prediction alone and form softmax(pred) / the pseudo-label themselves, fused; meters updated),
+        without its backward."""
         pred_2 = None
         if isinstance(pred, tuple):
             pred_2 = pred[1]
@@ -110,7 +120,7 @@ class UDATrainer(Trainer):
         self.source_loss(pred, y).backward()
 
     def train_target(self, pred):
-        """solve_gta5.py:178-218 (maxsquare / IW_maxsquare target modes)."""
+        """solve_gta5.py:178-218."""
         loss_target_ = self.target_loss_total(pred)
         if self.reducer:
             self.reducer.prepare_for_backward()

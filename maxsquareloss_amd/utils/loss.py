@@ -63,6 +63,50 @@ class IW_MaxSquareloss(nn.Module):
         return loss
 
 
+class softCrossEntropy(nn.Module):
+    """loss = mean over target != ignore_index of -log_softmax(inputs) * target (loss.py:17-35).
+    `target=None` is the trainer's call softCrossEntropy()(pred, softmax(pred)) (the `entropy` target
+    mode, target not detached) fused from the logits behind `inputs`: sum_px sum_c -lp_c p_c / (C*H*W)."""
+
+    def __init__(self, ignore_index=-1):
+        super().__init__()
+        self.ignore_index = ignore_index
+
+    def forward(self, inputs, target=None):
+        if target is None:
+            low, hw = _fused_source(inputs)
+            return ops.entropy_up(low, hw)
+        return ops.soft_ce(inputs, target, self.ignore_index)
+
+
+class IWsoftCrossEntropy(nn.Module):
+    """Image-wise class-balanced soft cross-entropy (loss.py:37-67).
+
+    hist = per-class pixel count of argmax(inputs) (the logits), weights as IW_MaxSquareloss,
+    loss = sum_px w[argmax] * sum_c -log_softmax(inputs)_c * target_c / (N*C) over target != ignore_index.
+    `target=None` is the `IW_entropy` target mode (target = softmax(inputs), not detached), fused.
+    The last histogram and weights are kept on the module (`last_hist`, `last_weights`)."""
+
+    def __init__(self, ignore_index=-1, num_class=19, ratio=0.2):
+        super().__init__()
+        self.ignore_index = ignore_index
+        self.num_class = num_class
+        self.ratio = ratio
+        self.last_hist = None
+        self.last_weights = None
+
+    def forward(self, inputs, target=None):
+        if inputs.size(1) != self.num_class:
+            raise ValueError(f"IWsoftCrossEntropy(num_class={self.num_class}) on {inputs.size(1)} channels")
+        if target is None:
+            low, hw = _fused_source(inputs)
+            loss, hist, w = ops.iw_entropy_up(low, hw, self.ratio)
+        else:
+            loss, hist, w = ops.iw_soft_ce(inputs, target, self.ratio, self.ignore_index)
+        self.last_hist, self.last_weights = hist, w
+        return loss
+
+
 class CrossEntropyLoss(nn.Module):
     """nn.CrossEntropyLoss(ignore_index=-1) on (1,C,H,W) logits and (1,H,W) int64 labels
     (train_source.py:128).  Mean over non-ignored pixels; nan when none (quirk Q8)."""
@@ -86,3 +130,11 @@ def multi_level_guidance_ce(pred, pred_2, threshold):
     if hw != hw2:
         raise ValueError("both heads must be upsampled to the same size")
     return ops.multi_ce_up(low1, low2.detach(), hw, threshold)
+
+
+def pseudo_label_ce(pred, threshold):
+    """The `hard` target mode (solve_gta5.py:185-199): CE(pred, label) with label = argmax softmax(pred)
+    where its maximum > threshold, else ignored (label detached); nan with a zero gradient when no pixel
+    passes (quirk Q8)."""
+    low, hw = _fused_source(pred)
+    return ops.hard_ce_up(low, hw, threshold)
