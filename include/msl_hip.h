@@ -545,6 +545,20 @@ int msl_bn_bwd_mask(const float* dy, const float* x, const uint64_t* relu_mask, 
 int msl_confusion_accumulate(const float* pred, const long long* label, int c, long long p,
                              unsigned long long* confusion, int* argmax_out, msl_stream_t stream);
 
+/* The evaluator's prediction (tools/evaluate.py:114-141) fused with that matrix, from the
+ * LOW-resolution head output logits[c][hi][wi]: every hi-res pixel of ho x wo is re-interpolated as
+ * the fused losses do (the hi-res logits / probabilities are never written).
+ *   logits_flip == NULL: class = np.argmax of up(logits) (lowest index on ties, NaN wins);
+ *   logits_flip != NULL (--flip; the low-res logits of the horizontally mirrored image): class =
+ *     np.argmax of (softmax(up(logits))[y][x] + softmax(up(logits_flip))[y][wo-1-x]) / 2.
+ * argmax_out (int32 [ho*wo], nullable) receives the class; label (int64 [ho*wo]) and confusion
+ * (uint64 [c*c], as msl_confusion_accumulate: confusion[gt * c + class] += 1, labels outside [0, c)
+ * skipped; exact, deterministic) are given together or both NULL (predict only).  At least one
+ * output is required; c <= 32; bad arguments or geometry are MSL_ERR_ARG. */
+int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                   const long long* label, unsigned long long* confusion, int32_t* argmax_out,
+                   msl_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Input pipeline (the loaders' last host steps, on the device after a uint8 H2D copy; byte-exact):
  *   msl_image_transform: out[c][y][x] = (float)rgb[y][xs][2 - c] - mean[c] (BGR order, mean =

@@ -823,6 +823,79 @@ __global__ void __launch_bounds__(256) k_pseudo_labels(const float* __restrict__
   }
 }
 
+// ---------------------------------------------------------------- evaluation: fused prediction
+// np.argmax over the classes (k_confusion's rule, eval.hip): the lowest index wins a tie and a NaN
+// counts as the maximum, so the first NaN is the answer.  Equal to argmax_first when no value is NaN.
+template <int CM>
+__device__ __forceinline__ int argmax_np(const float (&v)[CM], int C) {
+  float best = v[0];
+  int a = 0;
+  bool open = !(best != best);
+#pragma unroll
+  for (int c = 1; c < CM; ++c)
+    if (c < C && open) {
+      if (v[c] != v[c]) {
+        a = c;
+        open = false;
+      } else if (v[c] > best) {
+        best = v[c];
+        a = c;
+      }
+    }
+  return a;
+}
+
+// The evaluator's per-pixel class (tools/evaluate.py:114-141) from the LOW-resolution logits, and its
+// (gt, class) cell of the confusion matrix (utils/eval.py:109-115).  FLIP = 0: np.argmax of up(L).
+// FLIP = 1: np.argmax of (softmax(up(L))[y][x] + softmax(up(Lf))[y][Wo-1-x]) / 2, Lf the logits of the
+// mirrored image (the reference flips its probabilities back after upsampling).  The histogram is
+// k_confusion's: per-block LDS counts, integer atomics on the uint64 matrix - exact in any order.
+// label / cm and arg are nullable (the host requires one of them).
+template <int FLIP, int CM>
+__global__ void __launch_bounds__(256) k_predict_up(const float* __restrict__ L,
+                                                     const float* __restrict__ Lf, Geo g,
+                                                     const long long* __restrict__ label,
+                                                     unsigned long long* __restrict__ cm,
+                                                     int32_t* __restrict__ arg) {
+  __shared__ unsigned int h[kMaxC * kMaxC];
+  const int cc = g.C * g.C;
+  if (cm) {
+    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
+    __syncthreads();
+  }
+  const long long npx = (long long)g.Ho * g.Wo;  // < 2^31 (geo_ok); the stride may step past it
+  for (long long pp = blockIdx.x * 256LL + threadIdx.x; pp < npx; pp += (long long)gridDim.x * 256) {
+    const int px = (int)pp;
+    const int oy = px / g.Wo, ox = px - oy * g.Wo;
+    const Lin ly = lin(oy, g.sh, g.Hi), lx = lin(ox, g.sw, g.Wi);
+    float v[CM];
+    up_logits<CM>(L, g, ly, lx, v);
+    int best;
+    if (FLIP) {
+      float p[CM], q[CM], mx, sum;
+      softmax<CM>(v, g.C, p, mx, sum);
+      up_logits<CM>(Lf, g, ly, lin(g.Wo - 1 - ox, g.sw, g.Wi), v);
+      softmax<CM>(v, g.C, q, mx, sum);
+#pragma unroll
+      for (int c = 0; c < CM; ++c)
+        if (c < g.C) p[c] = (p[c] + q[c]) / 2.f;
+      best = argmax_np<CM>(p, g.C);
+    } else {
+      best = argmax_np<CM>(v, g.C);
+    }
+    if (arg) arg[px] = best;
+    if (cm) {
+      const long long y = label[px];
+      if (y >= 0 && y < g.C) atomicAdd(&h[(int)y * g.C + best], 1u);
+    }
+  }
+  if (cm) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < cc; i += 256)
+      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
+  }
+}
+
 // ---------------------------------------------------------------- host helpers
 static bool geo_ok(int c, int hi, int wi, int ho, int wo) {
   return c >= 1 && c <= kMaxC && hi >= 1 && wi >= 1 && ho >= 1 && wo >= 1 &&
@@ -1123,6 +1196,27 @@ int msl_pseudo_labels_up(const float* logits, int c, int hi, int wi, int ho, int
   MSL_DISPATCH_C(c, CM,
                  MSL_LAUNCH((k_pseudo_labels<CM>), dim3(nblk), dim3(256), 0, as_stream(stream),
                                     logits, g, thr, label, argmax_logits));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                   const long long* label, unsigned long long* confusion, int32_t* argmax_out,
+                   msl_stream_t stream) {
+  if (!geo_ok(c, hi, wi, ho, wo) || !logits || (label == nullptr) != (confusion == nullptr) ||
+      (!confusion && !argmax_out))
+    return MSL_ERR_ARG;
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  const int nblk = std::min(1024, cdiv((long long)ho * wo, 256));
+  hipStream_t st = as_stream(stream);
+  if (logits_flip)
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_predict_up<1, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
+                              g, label, confusion, argmax_out));
+  else
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_predict_up<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
+                              g, label, confusion, argmax_out));
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

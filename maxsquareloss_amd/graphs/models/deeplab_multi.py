@@ -269,6 +269,17 @@ class ResNetMulti(nn.Module):
         return [(ops.upsample_bilinear(a, input_size), ops.upsample_bilinear(b, input_size))
                 for a, b in zip(ops.pair_split(x2), ops.pair_split(x1))]
 
+    def predict_low(self, x, flip=False):
+        """The low-resolution (layer6, layer5) logits of x under torch.no_grad(), for the evaluator
+        (ops.predict_up upsamples on the fly).  With `flip`, x and its horizontal mirror run as one
+        image pair - every conv GEMM once over both; in eval mode both use the running statistics -
+        and the result is [(x2, x1), (x2_flip, x1_flip)] (tools/evaluate.py:114-131: two forwards)."""
+        with torch.no_grad():
+            if not flip:
+                return self._heads(x)
+            x2, x1 = self._heads(ops.pair_join(x, x.flip(-1)))
+            return list(zip(ops.pair_split(x2), ops.pair_split(x1)))
+
     def get_1x_lr_params_NOscale(self):
         """Backbone parameters, each yielded once per enclosing module (quirk Q2)."""
         b = [self.conv1, self.bn1, self.layer1, self.layer2, self.layer3, self.layer4]

@@ -92,6 +92,7 @@ SIGNATURES = {
     "msl_iw_maxsquare_prob_fwd": (c_int, [c_p, c_p, c_int, c_int, c_f, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "msl_iw_maxsquare_prob_bwd": (c_int, [c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
     "msl_confusion_accumulate": (c_int, [c_p, c_p, c_int, ctypes.c_longlong, c_p, c_p, c_p]),
+    "msl_predict_up": (c_int, [c_p, c_p] + [c_int] * 5 + [c_p, c_p, c_p, c_p]),
     "msl_bn_uses_fused": (c_int, [c_int, c_int, c_int, c_p]),
     "msl_bn_workspace": (c_sz, [c_int] * 3),
     "msl_bn_fwd": (c_int, [c_p] * 10 + [c_int] * 5 + [c_f, c_f, c_int, c_p, c_p, c_sz, c_p]),

@@ -1289,6 +1289,37 @@ def logits_argmax_up(low, out_hw):
     return _pseudo(low, out_hw, 0.0, False, True)[1]
 
 
+# --------------------------------------------------------------------------- evaluation
+def predict_up(low, out_hw, low_flip=None, label=None, confusion=None, want_argmax=False):
+    """The evaluator's per-pixel class (tools/evaluate.py:114-141) from the low-resolution logits
+    `low` (1,C,hi,wi), fused with the confusion matrix (msl_predict_up): np.argmax of the upsampled
+    logits, or - with `low_flip`, the low-res logits of the horizontally mirrored image - of
+    (softmax(up(low)) + mirror(softmax(up(low_flip)))) / 2.  `label` (int64, ho*wo elements) and
+    `confusion` (int64 [C*C] on the device, accumulated in place) go together; returns the int32
+    [ho*wo] class map when `want_argmax`, else None."""
+    low = _check_act(low.detach(), "predict_up")
+    c, hi, wi, ho, wo = _geom(low, out_hw)
+    if low_flip is not None:
+        low_flip = _check_act(low_flip.detach(), "predict_up")
+        if low_flip.shape != low.shape:
+            raise hip.MSLError("predict_up: low_flip must have low's shape")
+    if (label is None) != (confusion is None):
+        raise hip.MSLError("predict_up: label and confusion go together")
+    if label is not None:
+        label = label.contiguous()
+        if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
+            raise hip.MSLError(f"predict_up: label must be a CUDA int64 tensor with {ho * wo} elements")
+        if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
+                not confusion.is_contiguous()):
+            raise hip.MSLError(f"predict_up: confusion must be a contiguous CUDA int64 tensor with {c * c} elements")
+    elif not want_argmax:
+        raise hip.MSLError("predict_up: nothing to compute (no label / confusion and want_argmax=False)")
+    arg = torch.empty(ho * wo, dtype=torch.int32, device=low.device) if want_argmax else None
+    hip.check(hip.load().msl_predict_up(low.data_ptr(), hip.ptr(low_flip), c, hi, wi, ho, wo, hip.ptr(label),
+                                        hip.ptr(confusion), hip.ptr(arg), hip.stream_ptr()), "msl_predict_up")
+    return arg
+
+
 # --------------------------------------------------------------------------- soft cross-entropy, explicit target
 class _SoftCE(Function):
     """softCrossEntropy (ratio None) / IWsoftCrossEntropy on (1,C,H,W) logits and an explicit target."""
@@ -1445,8 +1476,10 @@ class _BNAct(Function):
         am = torch.empty(c, dtype=_f32, device=x.device) if _h3(CONV_MATH) else None
         # r05: a residual BN + ReLU under the fused kernels writes the ReLU mask as bits (msl_bn_fwd_mask),
         # so its backward reads 1 bit per pixel instead of y (msl_bn_bwd_mask)
+        # (only for a backward: under torch.no_grad() - the evaluator - no input needs a gradient and
+        # the bits would be written for nobody)
         bits = None
-        if relu and residual is not None and fused and BN_MASK_BITS:
+        if relu and residual is not None and fused and BN_MASK_BITS and any(ctx.needs_input_grad):
             bits = torch.empty(lib.msl_bn_relu_mask_bytes(c, p, n) // 8, dtype=torch.int64, device=x.device)
         hip.check(lib.msl_bn_fwd_mask(x.data_ptr(), hip.ptr(weight), hip.ptr(bias), hip.ptr(residual), y.data_ptr(),
                                       hip.ptr(running_mean), hip.ptr(running_var), hip.ptr(num_batches),

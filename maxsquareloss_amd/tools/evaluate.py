@@ -1,0 +1,118 @@
+"""Evaluator (tools/evaluate.py of the reference), MI355X path.
+
+Same surface: `Evaluater(args, cuda, train_id, logger)` with `main()`, `validate()` and
+`load_checkpoint()`; `validate()` returns (PA, MPA, MIoU, FWIoU) - for 16 classes the 13-class
+numbers -, logs the val_info lines and prints the per-class table (evaluate.py:99-202).  Run as
+
+    python -m maxsquareloss_amd.tools.evaluate --pretrained_ckpt_file best.pth --flip True
+
+What runs where (utils/validate.py): the eval-mode forward under torch.no_grad() down to the
+low-resolution head logits, then one HIP kernel (msl_predict_up) for upsampling, the class and the
+confusion matrix.  --flip (test-time augmentation, evaluate.py:120-135) runs the image and its
+mirror through the trunk as one pair and averages the two softmaxes inside that kernel.
+--graph True replays the per-image work as a captured hipGraph.  Differences from the reference:
+the val set is synthetic (--val_images items at target_crop_size, batch size 1, at most 500);
+tensorboard and image summaries are out.
+"""
+import argparse
+import logging
+import os
+
+import torch
+
+from .. import ops
+from ..utils.synthetic import init_weights
+from ..utils.train_helper import get_model
+from ..utils.validate import Validator, val_info
+from .train_source import add_train_args, init_args, str2bool
+
+
+class Evaluater:
+    def __init__(self, args, cuda=None, train_id=None, logger=None):
+        self.args = args
+        self.cuda = bool(cuda) and torch.cuda.is_available()
+        if not self.cuda:
+            raise RuntimeError("the MI355X evaluator needs a GPU (no CPU fallback)")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.current_MIoU = self.best_MIou = 0
+        self.current_epoch = self.current_iter = 0
+        self.train_id = train_id
+        self.logger = logger or logging.getLogger(__name__)
+
+        ops.set_conv_math(getattr(args, "conv_math", "fp32"))
+        if getattr(args, "f32_form", None):
+            ops.set_f32_form(args.f32_form)
+        self.model, _ = get_model(args)
+        init_weights(self.model, seed=args.seed)
+        self.model.to(self.device)
+
+        # evaluate.py:53-62: --pretrained_ckpt_file, else <checkpoint_dir's parent>/<train_id>best.pth
+        if args.pretrained_ckpt_file is not None:
+            path = args.pretrained_ckpt_file
+            if not os.path.exists(path):
+                parent = os.path.dirname(str(args.checkpoint_dir or "").rstrip("/"))
+                path = os.path.join(parent, str(train_id) + "best.pth")
+                if not os.path.exists(path):
+                    raise AssertionError("no pretrained_ckpt_file")
+            self.load_checkpoint(path)
+
+        w, h = args.target_crop_size
+        images = getattr(args, "val_images", 0) or args.synthetic_images
+        self.validator = Validator(self.model, args.num_classes, (h, w), images, self.device,
+                                   flip=bool(getattr(args, "flip", False)), graph=bool(getattr(args, "graph", False)))
+        self.Eval = self.validator.Eval
+        self.valid_iterations = self.validator.valid_iterations
+
+    def main(self):
+        self.logger.info("This model will run on %s", torch.cuda.get_device_name(self.device))
+        return self.validate()
+
+    def validate(self):
+        self.logger.info("validating one epoch...")
+        ev = self.validator.run()
+        out = val_info(ev, self.logger, self.current_epoch)
+        ev.Print_Every_class_Eval()
+        return out
+
+    def load_checkpoint(self, filename):
+        """evaluate.py:205-220: {'state_dict': ...} or a bare state dict ('module.' prefixes accepted);
+        a missing file is logged and skipped.  Read as data only (torch.load(weights_only=True))."""
+        try:
+            self.logger.info("Loading checkpoint '%s'", filename)
+            ckpt = torch.load(filename, map_location=self.device, weights_only=True)
+        except OSError:
+            self.logger.info("No checkpoint exists from '%s'. Skipping...", filename)
+            return
+        sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
+        self.model.load_state_dict({k[7:] if k.startswith("module.") else k: v for k, v in sd.items()})
+        self.logger.info("Checkpoint loaded successfully from %s", filename)
+        if "crop_size" in ckpt:
+            self.args.crop_size = ckpt["crop_size"]
+
+
+def build_parser():
+    parser = add_train_args(argparse.ArgumentParser())  # --val_images is one of the train flags
+    parser.add_argument("--flip", type=str2bool, default=False,
+                        help="average the softmax of the image and of its horizontal mirror (evaluate.py:120-135)")
+    parser.add_argument("--graph", type=str2bool, default=False,
+                        help="replay each image after the first as one captured hipGraph (not in the reference)")
+    return parser
+
+
+def parse_args(argv=None):
+    """evaluate.py:237-249: the val split, checkpoint_dir "none", crop = the target crop."""
+    args = build_parser().parse_args(argv)
+    if "train" in args.split:
+        args.split = "val"
+    if args.checkpoint_dir == "none":
+        args.checkpoint_dir = str(args.pretrained_ckpt_file) + "/eval"
+    args, train_id, logger = init_args(args)
+    args.crop_size = args.target_crop_size
+    args.base_size = args.target_base_size
+    return args, train_id, logger
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    args, train_id, logger = parse_args()
+    Evaluater(args=args, cuda=True, train_id=train_id, logger=logger).main()

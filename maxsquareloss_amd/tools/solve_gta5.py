@@ -310,6 +310,7 @@ class UDATrainer(Trainer):
     def train(self):
         for epoch in range(self.current_epoch, self.epoch_num):
             self.train_one_epoch(epoch)
+            self.validate_epoch()  # --val_images N > 0 (train_source.py)
             self.current_epoch += 1
         self.save_checkpoint(self.train_id + "final.pth")
 

@@ -13,6 +13,8 @@ the training arithmetic:
     the NaN check of :277-278 runs on the accumulated value at epoch end;
   - the per-iteration argmax + Eval confusion matrix (:280-283) run on the
     device (utils/eval.py, csrc/eval.hip), no D2H copy of the prediction;
+  - validation after each epoch (:180-213, :420-553) is opt-in: --val_images N
+    synthetic val items (default 0: none), `validate()`, best_MIou / best.pth;
     tensorboard logging is out of scope.
 """
 import argparse
@@ -32,6 +34,7 @@ from ..utils.loss import CrossEntropyLoss
 from ..utils.optim import SGD
 from ..utils.synthetic import SyntheticDomain, init_weights
 from ..utils.train_helper import get_model
+from ..utils.validate import Validator, val_info
 
 ITER_MAX = 5000
 
@@ -85,6 +88,8 @@ class Trainer:
         self.current_MIoU = self.best_MIou = self.best_FWIou = self.best_source_MIou = 0
         self.current_epoch = 0
         self.current_iter = 0
+        self.best_iter = 0
+        self._validator = None  # utils/validate.py, built by the first validate()
 
         self.loss = CrossEntropyLoss(weight=None, ignore_index=-1)
         self.Eval = Eval(self.args.num_classes)  # train_source.py:93, confusion matrix on device
@@ -123,8 +128,41 @@ class Trainer:
     def train(self):
         for epoch in range(self.current_epoch, self.epoch_num):
             self.train_one_epoch(epoch)
+            self.validate_epoch()
             self.current_epoch += 1
         self.save_checkpoint(self.train_id + "final.pth")
+
+    # ------------------------------------------------------------------ validation
+    def validate(self, epoch=None):
+        """train_source.py:420-553 (no flip, :448-459): the eval-mode forward of --val_images
+        synthetic val items at target_crop_size into a confusion matrix on the device
+        (utils/validate.py); returns (PA, MPA, MIoU, FWIoU), the 13-class numbers for 16 classes."""
+        if self._validator is None:
+            w, h = self.args.target_crop_size
+            self._validator = Validator(self.model, self.args.num_classes, (h, w), self.args.val_images,
+                                        self.device, rank=self.rank)
+        self.logger.info("validating one epoch...")
+        ev = self._validator.run()
+        out = val_info(ev, self.logger, self.current_epoch if epoch is None else epoch)
+        ev.Print_Every_class_Eval()
+        return out
+
+    def validate_epoch(self):
+        """train_source.py:180-213: after an epoch, with --val_images N > 0 (0, the default, trains
+        without validating): keep current_MIoU / best_MIou / best_iter, save <train_id>best.pth on
+        improvement."""
+        if getattr(self.args, "val_images", 0) <= 0:
+            return
+        PA, MPA, MIoU, FWIoU = self.validate(self.current_epoch)
+        self.current_MIoU = float(MIoU)  # a plain float: the checkpoint is read back as data only
+        if self.current_MIoU > self.best_MIou:
+            self.best_MIou = self.current_MIoU
+            self.best_iter = self.current_iter
+            self.logger.info("val MIoU %.5f is the best so far: saving %sbest.pth", self.best_MIou, self.train_id)
+            self.save_checkpoint(self.train_id + "best.pth")
+        else:
+            self.logger.info("val MIoU %.5f does not improve on %.5f (iteration %d)", self.current_MIoU,
+                             self.best_MIou, self.best_iter)
 
     def train_one_epoch(self, epoch=None):
         # train_source.py:225-229: --freeze_bn keeps BN on its running statistics
@@ -248,6 +286,9 @@ def add_train_args(arg_parser):
     a("--multi", default=True, type=str2bool)
     a("--lambda_seg", type=float, default=0.1)
     a("--synthetic_images", type=int, default=4, help="synthetic items per domain (no datasets offline)")
+    a("--val_images", type=int, default=0,
+      help="synthetic val items: with N > 0 the trainers validate after every epoch (best_MIou, "
+           "<train_id>best.pth), tools/evaluate.py evaluates N items; 0 = no validation while training")
     a("--conv_math", default="fp32", choices=["fp32", "fp16", "bf16"],
       help="conv MFMA precision (not in the reference, which is fp32): fp16 = BASELINE config 5's "
            "fp16 MFMA path (scaled fp16 operands, fp32 sums), bf16 = bf16 products, fp32 sums; BN, "

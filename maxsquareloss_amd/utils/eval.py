@@ -4,14 +4,20 @@ The reference bins `num_class * gt + argmax(pred)` with np.bincount after copyin
 prediction and label to the host every iteration (tools/train_source.py:280-283); here
 `add_batch(label, pred)` takes the device tensors and runs `msl_confusion_accumulate`
 (csrc/eval.hip: fused argmax + exact integer counts), and the matrix only crosses to the host
-when a metric is read.  The metric definitions follow utils/eval.py: per-class accuracy / IoU /
-precision with NaN for absent classes, nan-means over classes (`ignore_index` slicing),
+when a metric is read.  `add_batch_low` is the evaluator's form: from the low-resolution head
+logits, upsampling included (msl_predict_up), optionally with the --flip average.  The metric
+definitions follow utils/eval.py: per-class accuracy / IoU / precision with NaN for absent classes, nan-means over classes (`ignore_index` slicing),
 16/13-class SYNTHIA subsets, and FWIoU as the frequency-weighted sum of the non-NaN IoUs.
 """
 import numpy as np
 import torch
 
-from .. import hip
+from .. import hip, ops
+
+# the row names of Print_Every_class_Eval (datasets/cityscapes_Dataset.py:379-400)
+name_classes = ['road', 'sidewalk', 'building', 'wall', 'fence', 'pole', 'trafflight', 'traffsign', 'vegetation',
+                'terrain', 'sky', 'person', 'rider', 'car', 'truck', 'bus', 'train', 'motorcycle', 'bicycle',
+                'unlabeled']
 
 # utils/eval.py:9-11
 synthia_set_16 = [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 12, 13, 15, 17, 18]
@@ -53,6 +59,24 @@ class Eval:
             hip.check(lib.msl_confusion_accumulate(pred[n].data_ptr(), gt[n].data_ptr(), c, p,
                                                    self._dev.data_ptr(), None, hip.stream_ptr()),
                       "msl_confusion_accumulate")
+
+    def add_batch_low(self, gt_image, low, out_hw, low_flip=None):
+        """add_batch from the LOW-resolution logits `low` (1,C,hi,wi) of one image: the class of every
+        pixel of out_hw and its matrix cell in one kernel (ops.predict_up), the upsampled prediction
+        never written.  With `low_flip` (the mirrored image's low-res logits) the class is the
+        evaluator's --flip average (tools/evaluate.py:120-135); without, add_batch's argmax of
+        ops.upsample_bilinear(low, out_hw), bit for bit."""
+        if not (torch.is_tensor(low) and low.is_cuda and low.dim() == 4 and low.size(0) == 1):
+            raise hip.MSLError("Eval.add_batch_low: expects device logits [1, C, hi, wi]")
+        c = low.size(1)
+        if c != self.num_class:
+            raise hip.MSLError(f"Eval.add_batch_low: {c} classes, Eval built for {self.num_class}")
+        gt = gt_image.to(device=low.device, dtype=torch.int64).reshape(-1).contiguous()
+        if gt.numel() != int(out_hw[0]) * int(out_hw[1]):
+            raise hip.MSLError("Eval.add_batch_low: label and prediction sizes differ")
+        if self._dev is None or self._dev.device != low.device:
+            self._dev = torch.zeros(c * c, dtype=torch.int64, device=low.device)
+        ops.predict_up(low, out_hw, low_flip, gt, self._dev)
 
     def reset(self):
         self._host = np.zeros((self.num_class,) * 2)
@@ -117,3 +141,18 @@ class Eval:
         if out_16_13:
             return part(fw[synthia_set_16]), part(fw[synthia_set_13])
         return part(fw)
+
+    def Print_Every_class_Eval(self, out_16_13=False):
+        """The per-class table of utils/eval.py:90-106, character for character: accuracy, IoU,
+        precision, label share and prediction share in percent (round(., 2), 'nan' for an absent
+        class).  As there, out_16_13 shortens only the IoU column to the 16 SYNTHIA classes while the
+        row names and the other columns keep running over the first 16 indices."""
+        m = self.confusion_matrix
+        d, rows, cols, total = np.diag(m), m.sum(axis=1), m.sum(axis=0), m.sum()
+        iou = self._iou(m)
+        columns = [_ratio(d, rows), iou[synthia_set_16] if out_16_13 else iou, _ratio(d, cols),
+                   _ratio(rows, total), _ratio(cols, total)]
+        print('===>Everyclass:\t' + 'MPA\t' + 'MIoU\t' + 'PC\t' + 'Ratio\t' + 'Pred_Retio')
+        for i in range(len(columns[1])):
+            cells = [str(round(v[i] * 100, 2)) if not np.isnan(v[i]) else 'nan' for v in columns]
+            print('===>' + name_classes[i] + ':\t' + '\t'.join(cells))

@@ -1,0 +1,135 @@
+"""The validation loop of the reference (tools/evaluate.py:99-202; tools/train_source.py:420-553),
+MI355X path, shared by tools/evaluate.py's Evaluater and Trainer.validate.
+
+Per image: the eval-mode forward under torch.no_grad() down to the LOW-resolution head logits
+(ResNetMulti.predict_low; with --flip the image and its mirror as one pair), then one kernel
+(ops.predict_up, msl_predict_up) that re-interpolates every pixel, takes the reference's class -
+np.argmax of the upsampled logits, or of (softmax + mirrored softmax of the flipped image) / 2 -
+and counts it into the device confusion matrix.  The upsampled logits and probabilities are never
+written and nothing crosses to the host until a metric is read.
+
+`graph=True` captures that body once per shape as a hipGraph (GraphedPredict) and replays it with the
+image and label copied into static buffers.  The data is synthetic (utils/synthetic.py) at a fixed
+offset away from the training items.
+"""
+import gc
+
+import torch
+
+from .. import ops
+from .eval import Eval
+from .synthetic import SyntheticDomain
+
+VAL_OFFSET = 900          # the val items' seed offset (train: 0, UDA target: 500)
+VAL_ITER_MAX = 500        # evaluate.py:83: valid_iterations = min(num_iterations, 500)
+
+
+def predict_image(model, ev, x, y, hw, flip):
+    """One image into ev's matrix: x (1,3,H,W) fp32, y int64 (H*W labels), both on the device."""
+    if flip:
+        (low, _), (low_f, _) = model.predict_low(x, flip=True)
+        ev.add_batch_low(y, low, hw, low_f)
+    else:
+        ev.add_batch_low(y, model.predict_low(x)[0], hw)
+
+
+class GraphedPredict:
+    """predict_image as a captured graph, by utils/graph.py's rules: the first call runs eagerly on
+    the capture stream (that builds every weight pack and settles the allocator), then the body is
+    captured once - own stream, no garbage collection while capturing - and later calls copy the
+    image and label into the static buffers and replay.  The captured forward reads the weight packs
+    (ops.PackCache, rewritten in place) and not the conv weights: before a replay, if any parameter's
+    version differs from the versions the packs were built at, they are rebuilt eagerly first."""
+
+    def __init__(self, model, ev, hw, flip, device):
+        self.model, self.ev, self.hw, self.flip, self.device = model, ev, hw, flip, device
+        self.stream = torch.cuda.Stream(device=device)
+        self.packer = ops.PackBatch(model)
+        self.params = list(model.parameters())
+        self.graph = None
+        self.x = self.y = self.versions = None
+        self.replays = 0
+        self.eager_repacks = 0
+
+    def _repack(self):
+        self.packer.run()
+        for c, d in self.packer._jobs():  # whatever the batched launch left stale: the per-conv path
+            ws, cin, cout = c.meta[d]
+            if c.key[d] != c.key_of(ws):
+                c.get(ws, cin, cout, d)
+        self.versions = [p._version for p in self.params]
+
+    def __call__(self, x, y):
+        if self.graph is None:
+            return self._first(x, y)
+        self.x.copy_(x, non_blocking=True)
+        self.y.copy_(y.reshape(-1), non_blocking=True)
+        if any(p._version != v for p, v in zip(self.params, self.versions)):
+            self._repack()
+            self.eager_repacks += 1
+        self.graph.replay()
+        self.replays += 1
+
+    def _first(self, x, y):
+        self.x = x.to(self.device, copy=True)
+        self.y = y.to(self.device, dtype=torch.int64, copy=True).reshape(-1)
+        s = self.stream
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            predict_image(self.model, self.ev, self.x, self.y, self.hw, self.flip)  # image 0, eager
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        torch.cuda.synchronize(self.device)
+        self._repack()  # nothing stale now; records the versions the packs were built at
+        gc_was = gc.isenabled()
+        gc.disable()
+        try:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=s):
+                predict_image(self.model, self.ev, self.x, self.y, self.hw, self.flip)
+        finally:
+            if gc_was:
+                gc.enable()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+
+
+def val_info(ev, logger, epoch, name=""):
+    """The val_info lines of evaluate.py:170-195; returns (PA, MPA, MIoU, FWIoU), for 16 classes the
+    13-class numbers."""
+    PA = ev.Pixel_Accuracy()
+    MPA, MIoU, FWIoU, PC = (ev.Mean_Pixel_Accuracy(), ev.Mean_Intersection_over_Union(),
+                            ev.Frequency_Weighted_Intersection_over_Union(), ev.Mean_Precision())
+    print("########## Eval{} ############".format(name))
+    if ev.synthia:
+        for k, tag in ((0, "16"), (1, "13")):
+            logger.info('\nEpoch:{:.3f}, {} PA:{:.3f}, MPA_{t}:{:.3f}, MIoU_{t}:{:.3f}, FWIoU_{t}:{:.3f}, '
+                        'PC_{t}:{:.3f}'.format(epoch, name, PA, MPA[k], MIoU[k], FWIoU[k], PC[k], t=tag))
+        return PA, MPA[1], MIoU[1], FWIoU[1]
+    logger.info('\nEpoch:{:.3f}, {} PA1:{:.3f}, MPA1:{:.3f}, MIoU1:{:.3f}, FWIoU1:{:.3f}, PC:{:.3f}'.format(
+        epoch, name, PA, MPA, MIoU, FWIoU, PC))
+    return PA, MPA, MIoU, FWIoU
+
+
+class Validator:
+    def __init__(self, model, num_classes, hw, images, device, flip=False, graph=False, rank=0):
+        self.model, self.hw, self.device, self.flip, self.use_graph = model, (int(hw[0]), int(hw[1])), device, flip, graph
+        self.Eval = Eval(num_classes)
+        self.data = SyntheticDomain(self.hw[0], self.hw[1], num_classes, images, rank=rank, offset=VAL_OFFSET)
+        self.valid_iterations = min(len(self.data), VAL_ITER_MAX)
+        self._graphed = {}  # flip -> GraphedPredict (one capture per body; the shape is fixed)
+
+    def run(self):
+        """Fill self.Eval over the val items (model.eval(), no_grad); the model stays in eval mode, as
+        after the reference's validate()."""
+        self.Eval.reset()
+        self.model.eval()
+        with torch.no_grad():
+            for i in range(self.valid_iterations):
+                x, y, _ = self.data[i]
+                if self.use_graph:
+                    if self.flip not in self._graphed:
+                        self._graphed[self.flip] = GraphedPredict(self.model, self.Eval, self.hw, self.flip, self.device)
+                    self._graphed[self.flip](x, y)
+                else:
+                    predict_image(self.model, self.Eval, x.to(self.device, non_blocking=True),
+                                  y.to(self.device, dtype=torch.long, non_blocking=True).reshape(-1), self.hw, self.flip)
+        return self.Eval
