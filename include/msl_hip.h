@@ -576,6 +576,37 @@ int msl_label_transform(const uint8_t* ids, int h, int w, int mirror, const int3
                         int64_t* out, msl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Pillow-exact resampling (the loaders' Image.transpose / crop / resize, on the device; byte-exact
+ * against Pillow's 8-bit paths; datasets/cityscapes_Dataset.py:173-243).  The crop (x0, y0, cw, ch)
+ * is taken from the mirrored source (crop column x = source column mirror ? sw-1-(x0+x) : x0+x) and
+ * resized to (ow, oh); the tables are built for the CROP size (utils/resample.py).
+ *   msl_resize_bicubic_rgb: Image.BICUBIC on uint8 HWC RGB.  One pass per axis,
+ *       out = clamp((2^21 + sum_k px[first+k] * coeff[k]) >> 22, 0, 255), horizontal first into a uint8
+ *       intermediate (ws, msl_resize_workspace(ch, ow) bytes, needed only when both axes resize),
+ *       then vertical.  Per axis: xb / yb = HOST int32 [out][2] = (first, taps), read during the call
+ *       only (validated before anything is launched, and sizes the launch); xk / yk = DEVICE int32
+ *       [2 + ks][out] = row 0 the first taps, row 1 the tap counts, rows 2.. the ks 22-bit
+ *       coefficients of every output (transposed, so a wave's loads are contiguous); ks in 1..64.  Both NULL = no pass on that axis (then ow == cw / oh == ch).  The kernels clamp every
+ *       row's taps to the crop, so a device table that disagrees with the host bounds cannot read
+ *       outside the source.  Outputs (at least one): out_u8 uint8 HWC (oh, ow, 3); out_f32 fp32
+ *       (3, oh, ow) BGR - mean, as msl_image_transform, written by the last pass.
+ *   msl_resize_nearest_label: Image.NEAREST on a uint8 id map, a gather through xtab / ytab (DEVICE
+ *       int32 [ow] / [oh] source indices, clamped to the crop by the kernel; NULL = identity, then
+ *       ow == cw / oh == ch).  Outputs (at least one): out_u8 the raw ids (oh, ow); out_i64 =
+ *       lut256[id] (device int32[256], required with out_i64).
+ * MSL_ERR_ARG, before any launch: a crop outside the source, host bounds that leave the crop, ks
+ * outside 1..64, a missing table half, no output, a short workspace, a dimension over 65535.
+ * ---------------------------------------------------------------------- */
+size_t msl_resize_workspace(int ch, int ow);
+int msl_resize_bicubic_rgb(const uint8_t* src, int sh, int sw, int x0, int y0, int cw, int ch, int mirror,
+                           const int32_t* xb, const int32_t* xk, int xks, const int32_t* yb, const int32_t* yk,
+                           int yks, int ow, int oh, uint8_t* out_u8, float* out_f32, float mean_b, float mean_g,
+                           float mean_r, void* ws, size_t ws_bytes, msl_stream_t stream);
+int msl_resize_nearest_label(const uint8_t* ids, int sh, int sw, int x0, int y0, int cw, int ch, int mirror,
+                             const int32_t* xtab, const int32_t* ytab, int ow, int oh, const int32_t* lut256,
+                             uint8_t* out_u8, int64_t* out_i64, msl_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * SGD step with the reference's duplicated-parameter semantics (quirk Q2):
  * torch.optim.SGD(momentum, weight_decay) single-tensor loop over the
  * optim_parameters() groups (train_source.py:139-144, deeplab_multi.py:132-171),

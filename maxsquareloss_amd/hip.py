@@ -105,6 +105,10 @@ SIGNATURES = {
     "msl_bn_bwd_mask": (c_int, [c_p] * 11 + [c_int] * 6 + [c_p, c_p, c_sz, c_p, c_p]),
     "msl_image_transform": (c_int, [c_p, c_int, c_int, c_int, c_f, c_f, c_f, c_p, c_p]),
     "msl_label_transform": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
+    "msl_resize_workspace": (c_sz, [c_int, c_int]),
+    "msl_resize_bicubic_rgb": (c_int, [c_p] + [c_int] * 7 + [c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_int, c_p, c_p,
+                                       c_f, c_f, c_f, c_p, c_sz, c_p]),
+    "msl_resize_nearest_label": (c_int, [c_p] + [c_int] * 7 + [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
     "msl_im2col": (c_int, [c_p] + [c_int] * 11 + [c_p, c_p]),
     "msl_col2im": (c_int, [c_p] + [c_int] * 11 + [c_p, c_p]),
     "msl_maxpool_fwd": (c_int, [c_p] + [c_int] * 8 + [c_p, c_p, c_p]),

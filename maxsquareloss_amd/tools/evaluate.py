@@ -11,7 +11,8 @@ low-resolution head logits, then one HIP kernel (msl_predict_up) for upsampling,
 confusion matrix.  --flip (test-time augmentation, evaluate.py:120-135) runs the image and its
 mirror through the trunk as one pair and averages the two softmaxes inside that kernel.
 --graph True replays the per-image work as a captured hipGraph.  Differences from the reference:
-the val set is synthetic (--val_images items at target_crop_size, batch size 1, at most 500);
+the val set is the val split of --dataset under --data_root_path (datasets/, transformed on the
+device), or without a path synthetic (--val_images items at target_crop_size); batch size 1, at most 500;
 tensorboard and image summaries are out.
 """
 import argparse
@@ -24,7 +25,8 @@ from .. import ops
 from ..utils.synthetic import init_weights
 from ..utils.train_helper import get_model
 from ..utils.validate import Validator, val_info
-from .train_source import add_train_args, init_args, str2bool
+from ..datasets import build_loader
+from .train_source import add_train_args, dataset_paths, init_args, str2bool
 
 
 class Evaluater:
@@ -58,8 +60,14 @@ class Evaluater:
 
         w, h = args.target_crop_size
         images = getattr(args, "val_images", 0) or args.synthetic_images
+        # evaluate.py:64-79: with --data_root_path the val split of --dataset from files (batch size 1)
+        self.dataloader = None
+        if getattr(args, "data_root_path", None) is not None:
+            self.dataloader = build_loader(args.dataset, args, False, dataset_paths(
+                args.dataset, args.data_root_path, args.list_path, getattr(args, "gt_path", None)))
         self.validator = Validator(self.model, args.num_classes, (h, w), images, self.device,
-                                   flip=bool(getattr(args, "flip", False)), graph=bool(getattr(args, "graph", False)))
+                                   flip=bool(getattr(args, "flip", False)), graph=bool(getattr(args, "graph", False)),
+                                   data=self.dataloader.val_loader if self.dataloader else None)
         self.Eval = self.validator.Eval
         self.valid_iterations = self.validator.valid_iterations
 

@@ -17,32 +17,41 @@ same sums, added inside the weight-gradient GEMMs instead of by a second pass.
 
 The losses run fused from the low-resolution logits (utils/loss.py), so the
 two softmax tensors of the reference (:182-183) are never materialised.
-Style-transfer augmentation (exp_tag source_aug/target_aug) and the
-validation/eval path are out of scope.
+Style-transfer augmentation (exp_tag source_aug/target_aug) is out of scope
+(SURVEY.md §2, §8f).
+
+Data: with --source_data_path and --target_data_path the source (GTA5) and target
+(Cityscapes) items come from files (datasets/: Pillow decodes on --data_loader_workers
+threads, the reference's whole transform runs on the device, byte-exact); without
+them (the default) from the synthetic generator.
 """
 import argparse
+import copy
 import os
 
 import numpy as np
 import torch
 
 from .. import ops
+from ..datasets import build_loader
+from ..hip import MSLError
 from ..utils.loss import (IW_MaxSquareloss, IWsoftCrossEntropy, MaxSquareloss, multi_level_guidance_ce,
                           pseudo_label_ce, softCrossEntropy)
 from ..utils.graph import GraphedStep
 from ..utils.synthetic import SyntheticDomain
-from .train_source import Trainer, add_train_args, init_args, str2bool
+from .train_source import Trainer, add_train_args, dataset_paths, init_args, str2bool
 
 
 class UDATrainer(Trainer):
     def __init__(self, args, cuda=None, train_id="None", logger=None):
         super().__init__(args, cuda, train_id, logger)
-        h, w = self.args.crop_size[1], self.args.crop_size[0]
-        th, tw = self.args.target_crop_size[1], self.args.target_crop_size[0]
-        self.source_dataloader = SyntheticDomain(h, w, self.args.num_classes, self.args.synthetic_images,
-                                                 rank=self.rank)
-        self.target_dataloader = SyntheticDomain(th, tw, self.args.num_classes, self.args.synthetic_images,
-                                                 rank=self.rank, offset=500)
+        if not self.file_backed:
+            h, w = self.args.crop_size[1], self.args.crop_size[0]
+            th, tw = self.args.target_crop_size[1], self.args.target_crop_size[0]
+            self.source_dataloader = SyntheticDomain(h, w, self.args.num_classes, self.args.synthetic_images,
+                                                     rank=self.rank)
+            self.target_dataloader = SyntheticDomain(th, tw, self.args.num_classes, self.args.synthetic_images,
+                                                     rank=self.rank, offset=500)
         self.ignore_index = -1
         mode = self.args.target_mode
         if mode == "maxsquare":
@@ -70,6 +79,32 @@ class UDATrainer(Trainer):
         self.overlap = bool(getattr(self.args, "overlap", True))
         self.pair = bool(getattr(self.args, "pair", True))
         self._side = None
+
+    def build_dataloader(self):
+        """solve_gta5.py:40-110: with --source_data_path and --target_data_path (or --data_root_path) the
+        file-backed source (--source_dataset, --source_split) and target (--dataset, --split) loaders;
+        self.dataloader is the target's, whose val split validate() walks.  The target dataset takes
+        target_base_size / target_crop_size as its base / crop size.  Without paths: the synthetic
+        domains of Trainer."""
+        a = self.args
+        g = lambda k: getattr(a, k, None)  # noqa: E731
+        tgt_root, src_root = g("target_data_path") or g("data_root_path"), g("source_data_path")
+        if tgt_root is None and src_root is None:
+            return super().build_dataloader()
+        if tgt_root is None or src_root is None:
+            raise MSLError("file-backed UDA needs both --source_data_path and --target_data_path (or "
+                           "--data_root_path for the target); give both, or neither for the synthetic loaders")
+        self.file_backed = True
+        sargs = copy.copy(a)
+        sargs.split = a.source_split
+        self.source_loader = build_loader(a.source_dataset, sargs, True, dataset_paths(
+            a.source_dataset, src_root, g("source_list_path"), g("source_gt_path")))
+        targs = copy.copy(a)
+        targs.base_size, targs.crop_size = a.target_base_size, a.target_crop_size
+        self.dataloader = build_loader(a.dataset, targs, True, dataset_paths(
+            a.dataset, tgt_root, g("target_list_path") or g("list_path"), g("target_gt_path") or g("gt_path")))
+        self.source_dataloader, self.target_dataloader = self.source_loader.data_loader, self.dataloader.data_loader
+        self._source_items = self._target_items = None
 
     def _reset_meters(self):
         # zeroed in place once they exist: a captured step (utils/graph.py) adds into these tensors
@@ -320,8 +355,15 @@ class UDATrainer(Trainer):
         self.Eval.reset()  # solve_gta5.py:294 (the UDA loop resets but never fills it)
         self._reset_meters()
         for i in range(self.iter_num):
-            x_s, y_s, _ = self.source_dataloader[i % len(self.source_dataloader)]
-            x_t, _, _ = self.target_dataloader[i % len(self.target_dataloader)]
+            if self.file_backed:
+                # the two loaders have different lengths: each runs epoch after epoch on its own
+                if self._source_items is None:
+                    self._source_items, self._target_items = self.source_dataloader.cycle(), self.target_dataloader.cycle()
+                x_s, y_s, _ = next(self._source_items)
+                x_t, _, _ = next(self._target_items)
+            else:
+                x_s, y_s, _ = self.source_dataloader[i % len(self.source_dataloader)]
+                x_t, _, _ = self.target_dataloader[i % len(self.target_dataloader)]
             self.uda_step(x_s.to(self.device), y_s.to(self.device, dtype=torch.long), x_t.to(self.device))
         self.logger.info("epoch %d: source loss %.6f target loss %.6f", self.current_epoch,
                          float(self.loss_seg_value), float(self.loss_target_value))
@@ -332,6 +374,13 @@ def add_UDA_train_args(arg_parser):
     a = arg_parser.add_argument
     a("--source_dataset", default="gta5", type=str, choices=["gta5", "synthia"])
     a("--source_split", default="train", type=str)
+    for dom in ("source", "target"):
+        a(f"--{dom}_data_path", type=str, default=None,
+          help=f"data root of the file-backed {dom} dataset (solve_gta5.py:443-447 takes it from a hard-coded "
+               "table); with the source and the target root given the trainer reads files, else synthetic items")
+        a(f"--{dom}_list_path", type=str, default=None, help="its list directory (default: the data root)")
+        a(f"--{dom}_gt_path", type=str, default=None,
+          help="its label root (default <root>/labels for GTA5, <root>/gtFine for Cityscapes)")
     a("--init_round", type=int, default=0)
     a("--round_num", type=int, default=1)
     a("--epoch_each_round", type=int, default=2)

@@ -4,17 +4,19 @@ Same flags (add_train_args, :726-829), same `init_args` parsing (:832-883),
 same `Trainer` surface (`train()`, `train_one_epoch()`, `poly_lr_scheduler`,
 `save_checkpoint` / `load_checkpoint` dict format).  Differences, all outside
 the training arithmetic:
-  - data is synthetic (the GTA5/Cityscapes/SYNTHIA files are not available):
-    utils/synthetic.py reproduces the reference preprocessing on generated
-    uint8 images; the dataset flags are accepted and only set shapes/classes;
+  - data: with --data_root_path the file-backed loader of --dataset (datasets/:
+    Pillow decodes, the whole transform runs on the device, byte-exact); without
+    it (the default) utils/synthetic.py's generated uint8 images through the
+    reference preprocessing, the dataset flags only setting shapes/classes;
   - one process per GPU: under torchrun (WORLD_SIZE > 1) the model is
     replicated and gradients are all-reduced over RCCL (utils/dist.py);
   - loss scalars stay on the device (no per-iteration .cpu().item() sync);
     the NaN check of :277-278 runs on the accumulated value at epoch end;
   - the per-iteration argmax + Eval confusion matrix (:280-283) run on the
     device (utils/eval.py, csrc/eval.hip), no D2H copy of the prediction;
-  - validation after each epoch (:180-213, :420-553) is opt-in: --val_images N
-    synthetic val items (default 0: none), `validate()`, best_MIou / best.pth;
+  - validation after each epoch (:180-213, :420-553): the file-backed loader's
+    val split, or opt-in --val_images N synthetic val items (default 0: none),
+    `validate()`, best_MIou / best.pth;
     tensorboard logging is out of scope.
 """
 import argparse
@@ -27,6 +29,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
+from ..datasets import build_loader
 from ..utils.dist import GradReducer
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.eval import Eval
@@ -63,6 +66,23 @@ def _free_port():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         return sk.getsockname()[1]
+
+
+def dataset_paths(dataset, data_root_path, list_path, gt_path=None):
+    """The {data_root_path, list_path, gt_path} of one file-backed dataset.  Without a gt path the
+    reference's layout (train_source.py:27-60): Cityscapes <root>/gtFine beside the images'
+    <root>/leftImg8bit..., GTA5 <root>/labels; the list path defaults to the data root."""
+    if gt_path is None:
+        gt_path = os.path.join(data_root_path, "labels" if str(dataset).lower() == "gta5" else "gtFine")
+    return {"data_root_path": data_root_path, "list_path": list_path or data_root_path, "gt_path": gt_path}
+
+
+def train_items(loader, n):
+    """n training items of a loader: a synthetic domain by index, a file-backed loader's
+    `data_loader` epoch after epoch (a new seeded permutation each)."""
+    if isinstance(loader, SyntheticDomain):
+        return (loader[i % len(loader)] for i in range(n))
+    return (item for _, item in zip(range(n), loader.data_loader.cycle()))
 
 
 class Trainer:
@@ -108,12 +128,24 @@ class Trainer:
         self.reducer = GradReducer(self.optimizer, always=self.world == 1) if dp else None
         self.packer = ops.PackBatch(self.model)  # every weight pack of a step in two launches
 
-        h, w = self.args.crop_size[1], self.args.crop_size[0]
-        self.dataloader = SyntheticDomain(h, w, self.args.num_classes, self.args.synthetic_images,
-                                          rank=self.rank)
-        self.dataloader.num_iterations = min(len(self.dataloader), ITER_MAX)
+        self.build_dataloader()
+        self.dataloader.num_iterations = min(self.dataloader.num_iterations, ITER_MAX)
         iters = self.args.iter_stop if self.args.iter_stop is not None else self.args.iter_max
         self.epoch_num = -(-iters // self.dataloader.num_iterations)
+
+    def build_dataloader(self):
+        """self.dataloader: with --data_root_path the file-backed loader of --dataset over
+        --data_root_path / --list_path / --gt_path (train_source.py:146-155); without it (the default)
+        the synthetic domain at crop_size."""
+        self.file_backed = getattr(self.args, "data_root_path", None) is not None
+        if self.file_backed:
+            self.dataloader = build_loader(self.args.dataset, self.args, True, dataset_paths(
+                self.args.dataset, self.args.data_root_path, self.args.list_path, getattr(self.args, "gt_path", None)))
+        else:
+            h, w = self.args.crop_size[1], self.args.crop_size[0]
+            self.dataloader = SyntheticDomain(h, w, self.args.num_classes, self.args.synthetic_images,
+                                              rank=self.rank)
+            self.dataloader.num_iterations = len(self.dataloader)
 
     # ------------------------------------------------------------------ loop
     def main(self):
@@ -140,18 +172,26 @@ class Trainer:
         if self._validator is None:
             w, h = self.args.target_crop_size
             self._validator = Validator(self.model, self.args.num_classes, (h, w), self.args.val_images,
-                                        self.device, rank=self.rank)
+                                        self.device, rank=self.rank, data=self.val_data())
         self.logger.info("validating one epoch...")
         ev = self._validator.run()
         out = val_info(ev, self.logger, self.current_epoch if epoch is None else epoch)
         ev.Print_Every_class_Eval()
         return out
 
+    def val_data(self):
+        """The val items: the file-backed loader's val_loader (train_source.py:420-553 walks
+        self.dataloader.val_loader), None = --val_images synthetic ones."""
+        return self.dataloader.val_loader if self.file_backed else None
+
+    def validates(self):
+        return self.file_backed or getattr(self.args, "val_images", 0) > 0
+
     def validate_epoch(self):
         """train_source.py:180-213: after an epoch, with --val_images N > 0 (0, the default, trains
         without validating): keep current_MIoU / best_MIou / best_iter, save <train_id>best.pth on
         improvement."""
-        if getattr(self.args, "val_images", 0) <= 0:
+        if not self.validates():
             return
         PA, MPA, MIoU, FWIoU = self.validate(self.current_epoch)
         self.current_MIoU = float(MIoU)  # a plain float: the checkpoint is read back as data only
@@ -170,8 +210,7 @@ class Trainer:
         iter_num = self.dataloader.num_iterations
         loss_sum = torch.zeros((), device=self.device)
         self.Eval.reset()
-        for i in range(iter_num):
-            x, y, _ = self.dataloader[i]
+        for x, y, _ in train_items(self.dataloader, iter_num):
             self.poly_lr_scheduler(self.optimizer, init_lr=self.args.lr, iter=self.current_iter,
                                    max_iter=self.args.iter_max, power=self.args.poly_power)
             x = x.to(self.device, non_blocking=True)
@@ -244,6 +283,9 @@ def add_train_args(arg_parser):
     a = arg_parser.add_argument
     a("--data_root_path", type=str, default=None)
     a("--list_path", type=str, default=None)
+    a("--gt_path", type=str, default=None,
+      help="label root of --data_root_path (not a flag of the reference, which hard-codes it): default "
+           "<data_root_path>/gtFine for Cityscapes, <data_root_path>/labels for GTA5")
     a("--checkpoint_dir", default=None)
     a("--save_dir", default="./log/train")
     a("--backbone", default="deeplabv2_multi")
@@ -263,7 +305,8 @@ def add_train_args(arg_parser):
     a("--target_crop_size", default="928,464", type=str)
     a("--seg_size", default=(1280, 640))
     a("--num_classes", default=19, type=int)
-    a("--data_loader_workers", default=0, type=int)
+    a("--data_loader_workers", default=0, type=int,
+      help="threads that decode PNGs ahead of the step (file-backed datasets; at most 16)")
     a("--pin_memory", default=2, type=int)
     a("--split", type=str, default="train")
     a("--random_mirror", default=True, type=str2bool)

@@ -8,11 +8,17 @@ bytes) and converted on the GPU (csrc/preprocess.hip), bit-exact:
   label_transform:  ids uint8 HW  -> trainIds int64 (1,H,W), -1 = ignore
                     (id2trainId + the 16 / 13-class remaps, :124-155, 260-264)
 both with the optional horizontal mirror of the random_mirror augmentation.
+
+resize_image / resize_label run what comes before that in the reference's _train_sync_transform /
+_val_sync_transform (:173-243) - Image.transpose, crop, resize with BICUBIC / NEAREST - byte-exact
+against Pillow on the device (csrc/resample.hip, tables from utils/resample.py), ending in the same
+two transforms.
 """
 import numpy as np
 import torch
 
 from .. import hip
+from . import resample
 from .synthetic import IMG_MEAN
 
 # id -> trainId tables of the three loaders (values not listed map to the ignore label -1)
@@ -73,4 +79,112 @@ def label_transform(ids, lut, mirror=False):
     out = torch.empty((1, h, w), dtype=torch.int64, device=ids.device)
     hip.check(hip.load().msl_label_transform(ids.data_ptr(), h, w, int(bool(mirror)), dlut.data_ptr(),
                                              out.data_ptr(), hip.stream_ptr()), "msl_label_transform")
+    return out
+
+
+# ---------------------------------------------------------------------------- Pillow-exact resampling
+_TABLES = {}  # (device index, kind, in, out) -> (host bounds or None, device table, ksize)
+
+
+def _bicubic_tables(in_size, out_size, device):
+    """Host bounds + the device table of msl_resize_bicubic_rgb ([2 + ksize][out]: first taps, tap
+    counts, coefficients), cached."""
+    key = (device.index, "bicubic", int(in_size), int(out_size))
+    got = _TABLES.get(key)
+    if got is None:
+        bounds, coeffs, ksize = resample.bicubic_table(in_size, out_size)
+        if ksize > resample.MAX_KSIZE:
+            raise hip.MSLError(f"resize_image: {in_size} -> {out_size} needs {ksize} taps per output; the "
+                               f"kernels take at most {resample.MAX_KSIZE}")
+        host = np.ascontiguousarray(bounds, np.int32)
+        dev = torch.from_numpy(np.ascontiguousarray(np.concatenate([bounds, coeffs], axis=1).T, np.int32)).to(device)
+        got = _TABLES[key] = (host, dev, ksize)
+    return got
+
+
+def _nearest_table(in_size, out_size, device):
+    key = (device.index, "nearest", int(in_size), int(out_size))
+    got = _TABLES.get(key)
+    if got is None:
+        got = _TABLES[key] = torch.from_numpy(np.array(resample.nearest_table(in_size, out_size), np.int32)).to(device)
+    return got
+
+
+def _crop_of(crop, h, w, what):
+    if crop is None:
+        return 0, 0, w, h
+    x1, y1, cw, ch = (int(v) for v in crop)
+    if x1 < 0 or y1 < 0 or cw < 1 or ch < 1 or x1 + cw > w or y1 + ch > h:
+        raise hip.MSLError(f"{what}: crop {tuple(crop)} leaves the {w}x{h} source")
+    return x1, y1, cw, ch
+
+
+def resize_image(rgb, out_wh, crop=None, mirror=False, mean=IMG_MEAN, as_uint8=False):
+    """Pillow's `img.transpose(FLIP_LEFT_RIGHT)` (if mirror), `img.crop((x1, y1, x1+w, y1+h))` (if
+    crop = (x1, y1, w, h), in the mirrored image) and `img.resize(out_wh, Image.BICUBIC)`, byte-exact,
+    on the device (csrc/resample.hip).  rgb: uint8 (H, W, 3) on the GPU; out_wh = (width, height).
+    Returns (1, 3, oh, ow) fp32 BGR - mean (the reference's _img_transform, written by the last
+    resampling pass), or with as_uint8 the resized uint8 (oh, ow, 3) image."""
+    if not rgb.is_cuda or rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.size(2) != 3:
+        raise hip.MSLError(f"resize_image: expected a CUDA uint8 (H, W, 3) tensor, got {tuple(rgb.shape)} "
+                           f"{rgb.dtype} {rgb.device}")
+    rgb = rgb.contiguous()
+    h, w = rgb.shape[:2]
+    ow, oh = int(out_wh[0]), int(out_wh[1])
+    x1, y1, cw, ch = _crop_of(crop, h, w, "resize_image")
+    lib = hip.load()
+    xb, xk, xks = _bicubic_tables(cw, ow, rgb.device) if ow != cw else (None, None, 0)
+    yb, yk, yks = _bicubic_tables(ch, oh, rgb.device) if oh != ch else (None, None, 0)
+    ws, ws_bytes = None, 0
+    if xk is not None and yk is not None:
+        ws_bytes = lib.msl_resize_workspace(ch, ow)
+        ws = hip.workspace(ws_bytes, rgb.device)
+    if as_uint8:
+        out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=rgb.device)
+        out_u8, out_f32 = out.data_ptr(), None
+    else:
+        out = torch.empty((1, 3, oh, ow), dtype=torch.float32, device=rgb.device)
+        out_u8, out_f32 = None, out.data_ptr()
+    m = [float(np.float32(v)) for v in mean]
+    hip.check(lib.msl_resize_bicubic_rgb(
+        rgb.data_ptr(), h, w, x1, y1, cw, ch, int(bool(mirror)),
+        None if xb is None else xb.ctypes.data, hip.ptr(xk), xks,
+        None if yb is None else yb.ctypes.data, hip.ptr(yk), yks, ow, oh, out_u8, out_f32, m[0], m[1], m[2],
+        hip.ptr(ws), ws_bytes, hip.stream_ptr()), "msl_resize_bicubic_rgb")
+    return out
+
+
+def _device_lut(lut, device):
+    key = (device.index, np.asarray(lut, np.int32).tobytes())
+    dlut = _LUTS.get(key)
+    if dlut is None:
+        dlut = torch.from_numpy(np.asarray(lut, np.int32).copy()).to(device)
+        if dlut.numel() != 256:
+            raise hip.MSLError("the id -> trainId table must have 256 entries")
+        _LUTS[key] = dlut
+    return dlut
+
+
+def resize_label(ids, out_wh, lut, crop=None, mirror=False):
+    """The label side of resize_image: mirror, crop, `mask.resize(out_wh, Image.NEAREST)`, byte-exact,
+    then the id -> trainId table.  ids: uint8 (H, W) on the GPU.  With lut (int32[256], build_lut)
+    returns (1, oh, ow) int64 trainIds; with lut=None the resized uint8 (oh, ow) id map."""
+    if not ids.is_cuda or ids.dtype != torch.uint8 or ids.dim() != 2:
+        raise hip.MSLError(f"resize_label: expected a CUDA uint8 (H, W) tensor, got {tuple(ids.shape)} "
+                           f"{ids.dtype} {ids.device}")
+    ids = ids.contiguous()
+    h, w = ids.shape
+    ow, oh = int(out_wh[0]), int(out_wh[1])
+    x1, y1, cw, ch = _crop_of(crop, h, w, "resize_label")
+    xtab = _nearest_table(cw, ow, ids.device) if ow != cw else None
+    ytab = _nearest_table(ch, oh, ids.device) if oh != ch else None
+    if lut is None:
+        out = torch.empty((oh, ow), dtype=torch.uint8, device=ids.device)
+        dlut, out_u8, out_i64 = None, out.data_ptr(), None
+    else:
+        out = torch.empty((1, oh, ow), dtype=torch.int64, device=ids.device)
+        dlut, out_u8, out_i64 = _device_lut(lut, ids.device), None, out.data_ptr()
+    hip.check(hip.load().msl_resize_nearest_label(
+        ids.data_ptr(), h, w, x1, y1, cw, ch, int(bool(mirror)), hip.ptr(xtab), hip.ptr(ytab), ow, oh,
+        hip.ptr(dlut), out_u8, out_i64, hip.stream_ptr()), "msl_resize_nearest_label")
     return out

@@ -9,8 +9,9 @@ and counts it into the device confusion matrix.  The upsampled logits and probab
 written and nothing crosses to the host until a metric is read.
 
 `graph=True` captures that body once per shape as a hipGraph (GraphedPredict) and replays it with the
-image and label copied into static buffers.  The data is synthetic (utils/synthetic.py) at a fixed
-offset away from the training items.
+image and label copied into static buffers.  The data is whatever the caller hands the Validator - a
+file-backed val loader (datasets/) - or, by default, synthetic (utils/synthetic.py) at a fixed offset
+away from the training items.
 """
 import gc
 
@@ -110,12 +111,21 @@ def val_info(ev, logger, epoch, name=""):
 
 
 class Validator:
-    def __init__(self, model, num_classes, hw, images, device, flip=False, graph=False, rank=0):
+    def __init__(self, model, num_classes, hw, images, device, flip=False, graph=False, rank=0, data=None):
+        """`data`: any iterable of (image (1,3,H,W), label, id) items with a length - a file-backed val
+        loader (datasets/), a list of tensors; None = `images` synthetic items of size hw."""
         self.model, self.hw, self.device, self.flip, self.use_graph = model, (int(hw[0]), int(hw[1])), device, flip, graph
         self.Eval = Eval(num_classes)
-        self.data = SyntheticDomain(self.hw[0], self.hw[1], num_classes, images, rank=rank, offset=VAL_OFFSET)
+        if data is None:
+            data = SyntheticDomain(self.hw[0], self.hw[1], num_classes, images, rank=rank, offset=VAL_OFFSET)
+        self.data = data
         self.valid_iterations = min(len(self.data), VAL_ITER_MAX)
-        self._graphed = {}  # flip -> GraphedPredict (one capture per body; the shape is fixed)
+        self._graphed = {}  # flip [, image size when it is not hw] -> GraphedPredict (one capture per body and shape)
+
+    def _items(self):
+        if isinstance(self.data, SyntheticDomain):
+            return (self.data[i] for i in range(self.valid_iterations))
+        return (item for _, item in zip(range(self.valid_iterations), self.data))
 
     def run(self):
         """Fill self.Eval over the val items (model.eval(), no_grad); the model stays in eval mode, as
@@ -123,13 +133,14 @@ class Validator:
         self.Eval.reset()
         self.model.eval()
         with torch.no_grad():
-            for i in range(self.valid_iterations):
-                x, y, _ = self.data[i]
+            for x, y, _ in self._items():
+                hw = (int(x.shape[-2]), int(x.shape[-1]))  # the item's own size (file-backed: the val resize)
                 if self.use_graph:
-                    if self.flip not in self._graphed:
-                        self._graphed[self.flip] = GraphedPredict(self.model, self.Eval, self.hw, self.flip, self.device)
-                    self._graphed[self.flip](x, y)
+                    key = self.flip if hw == self.hw else (self.flip, hw)
+                    if key not in self._graphed:
+                        self._graphed[key] = GraphedPredict(self.model, self.Eval, hw, self.flip, self.device)
+                    self._graphed[key](x, y)
                 else:
                     predict_image(self.model, self.Eval, x.to(self.device, non_blocking=True),
-                                  y.to(self.device, dtype=torch.long, non_blocking=True).reshape(-1), self.hw, self.flip)
+                                  y.to(self.device, dtype=torch.long, non_blocking=True).reshape(-1), hw, self.flip)
         return self.Eval
