@@ -640,6 +640,48 @@ int msl_sgd_step_lr_dev(const msl_sgd_entry* entries, const int32_t* block_entry
                         const long long* block_offset, long long n_blocks, const float* lr_dev,
                         float momentum, float weight_decay, float grad_scale, msl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Adam with the same duplicated-parameter semantics: torch.optim.Adam(params,
+ * betas, eps, weight_decay) (amsgrad=False, L2 weight decay; train_source.py:145-146),
+ * single-tensor loop, where a parameter listed k times receives k sequential
+ * updates sharing exp_avg, exp_avg_sq and the step counter, which advances by k.
+ * Per update:  step += 1;  d = g*grad_scale + wd*p;  m += (1-b1)*(d-m);
+ * v = v*b2 + (1-b2)*d*d;  p -= lr/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps).
+ * ---------------------------------------------------------------------- */
+typedef struct msl_adam_entry {
+  float* param;       /* updated in place */
+  const float* grad;  /* read-only */
+  float* exp_avg;     /* first moment, updated in place */
+  float* exp_avg_sq;  /* second moment, updated in place */
+  float* step;        /* DEVICE fp32 scalar: updates applied so far (torch's state['step']); advanced by mult */
+  long long numel;
+  int mult;           /* occurrences of this parameter in its group: 1..msl_adam_max_mult() */
+  int group;          /* 0: backbone (lr), 1: ASPP heads (10*lr) */
+} msl_adam_entry;
+
+/* The block plan is msl_sgd_plan's (chunks of msl_sgd_block_elems() elements).  A step is two
+ * launches on `stream`: one thread per entry reads the entry's counter and its group's rate,
+ * computes in double lr/(1-b1^t) and sqrt(1-b2^t) for t = step+1 .. step+mult, rounds them to
+ * fp32 into coef (DEVICE, msl_adam_coef_bytes(n_entries) bytes: [n_entries][msl_adam_max_mult()][2]
+ * floats, no initialisation needed) and stores step + mult; the element kernel then reads coef only,
+ * never the counters, so no block sees a counter that another block of the step has advanced, and
+ * a captured hipGraph replays the pair with the counters advancing on the device.  mult above
+ * msl_adam_max_mult() (4) is applied as 4.  beta1, beta2, eps are doubles as torch holds them
+ * (1-beta rounded to fp32 once).  MSL_ERR_ARG: a NULL table or coef, a negative count, a beta
+ * outside [0, 1), eps < 0.  n_blocks == 0 launches no element kernel (MSL_OK). */
+int msl_adam_max_mult(void);
+size_t msl_adam_coef_bytes(int n_entries);
+int msl_adam_step(const msl_adam_entry* entries, int n_entries, const int32_t* block_entry,
+                  const long long* block_offset, long long n_blocks, float lr0, float lr1, double beta1,
+                  double beta2, double eps, float weight_decay, float grad_scale, float* coef,
+                  msl_stream_t stream);
+/* The same step with the two group learning rates read from device memory (by the coefficient
+ * launch) when the step runs, as msl_sgd_step_lr_dev. */
+int msl_adam_step_lr_dev(const msl_adam_entry* entries, int n_entries, const int32_t* block_entry,
+                         const long long* block_offset, long long n_blocks, const float* lr_dev,
+                         double beta1, double beta2, double eps, float weight_decay, float grad_scale,
+                         float* coef, msl_stream_t stream);
+
 /* Diagnostics (r06): the launch guard every entry point runs before each kernel launch (MSL_ERR_LAUNCH
  * when a block exceeds the kernel's __launch_bounds__).  Launches a 256-thread-bound probe kernel with
  * `threads` threads writing out[t] = t: MSL_OK (and out[0 .. threads) written) for 1 <= threads <= 256,

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MSL_LIB_PATH") or os.path.join(os.path.dirname(os.pat
                                                           "libmsl_hip.so")
 
 c_int, c_ll, c_sz, c_f, c_p = ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_float, ctypes.c_void_p
+c_d = ctypes.c_double
 
 # name -> (restype, argtypes); must match include/msl_hip.h exactly.
 SIGNATURES = {
@@ -123,6 +124,10 @@ SIGNATURES = {
     "msl_sgd_plan": (c_ll, [c_p, c_int, c_p, c_p, c_ll]),
     "msl_sgd_step": (c_int, [c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_f, c_p]),
     "msl_sgd_step_lr_dev": (c_int, [c_p, c_p, c_p, c_ll, c_p, c_f, c_f, c_f, c_p]),
+    "msl_adam_max_mult": (c_int, []),
+    "msl_adam_coef_bytes": (c_sz, [c_int]),
+    "msl_adam_step": (c_int, [c_p, c_int, c_p, c_p, c_ll, c_f, c_f, c_d, c_d, c_d, c_f, c_f, c_p, c_p]),
+    "msl_adam_step_lr_dev": (c_int, [c_p, c_int, c_p, c_p, c_ll, c_p, c_d, c_d, c_d, c_f, c_f, c_p, c_p]),
     "msl_launch_guard_probe": (c_int, [c_int, c_p, c_p]),
     "msl_pconv_dgrad_resmask_sc": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_p, c_p, c_sz, c_p, c_p,
                                            c_int]),

@@ -34,7 +34,7 @@ from ..utils.dist import GradReducer
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
 from ..utils.eval import Eval
 from ..utils.loss import CrossEntropyLoss
-from ..utils.optim import SGD
+from ..utils.optim import SGD, Adam
 from ..utils.synthetic import SyntheticDomain, init_weights
 from ..utils.train_helper import get_model
 from ..utils.validate import Validator, val_info
@@ -121,10 +121,7 @@ class Trainer:
         init_weights(self.model, seed=self.args.seed)
         self.model.to(self.device)
 
-        if self.args.optim != "SGD":
-            raise NotImplementedError("only --optim SGD (the reference default) is on the MI355X path")
-        self.optimizer = SGD(lr=self.args.lr, params=self.params, momentum=self.args.momentum,
-                             weight_decay=self.args.weight_decay)
+        self.optimizer = self.build_optimizer()
         self.reducer = GradReducer(self.optimizer, always=self.world == 1) if dp else None
         self.packer = ops.PackBatch(self.model)  # every weight pack of a step in two launches
 
@@ -132,6 +129,18 @@ class Trainer:
         self.dataloader.num_iterations = min(self.dataloader.num_iterations, ITER_MAX)
         iters = self.args.iter_stop if self.args.iter_stop is not None else self.args.iter_max
         self.epoch_num = -(-iters // self.dataloader.num_iterations)
+
+    def build_optimizer(self):
+        """train_source.py:139-146: --optim SGD (lr, momentum, weight_decay) or Adam (betas (0.9, 0.99),
+        weight_decay; the groups' own lr entries and the poly scheduler set its rates) over
+        self.params, the model's optim_parameters() groups."""
+        if self.args.optim == "SGD":
+            return SGD(lr=self.args.lr, params=self.params, momentum=self.args.momentum,
+                       weight_decay=self.args.weight_decay)
+        if self.args.optim == "Adam":
+            return Adam(self.params, betas=(0.9, 0.99), weight_decay=self.args.weight_decay)
+        raise NotImplementedError(f"--optim {self.args.optim}: only SGD (the reference default) and Adam are on "
+                                  "the MI355X path")
 
     def build_dataloader(self):
         """self.dataloader: with --data_root_path the file-backed loader of --dataset over

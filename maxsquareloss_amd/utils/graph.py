@@ -8,9 +8,10 @@ handles, the SGD launch table with the reference's first-step momentum rule (qui
 live parameter set - then captures the iteration body once and replays it for every later
 iteration:
   - inputs are copied into the captured (static) buffers before each replay;
-  - the poly learning rates (train_source.py:706-717) change every iteration: the captured SGD
-    kernel reads them from device memory (msl_sgd_step_lr_dev), refreshed from a pinned host
-    ring before each replay;
+  - the poly learning rates (train_source.py:706-717) change every iteration: the captured
+    optimizer step reads them from device memory (msl_sgd_step_lr_dev; --optim Adam:
+    msl_adam_step_lr_dev, whose per-parameter step counters also live on the device and are
+    advanced by the captured launch itself), refreshed from a pinned host ring before each replay;
   - every weight pack (ops.PackCache) and the SGD step are inside the graph, so each replay
     repacks from the weights the previous replay updated; after a replay the parameters'
     version counters are bumped so eager code outside the graph repacks too, and recorded: a
