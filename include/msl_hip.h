@@ -40,7 +40,9 @@ typedef void* msl_stream_t; /* a hipStream_t */
 #define MSL_ERR_SHAPE (-1)
 #define MSL_ERR_WORKSPACE (-2)
 #define MSL_ERR_ARG (-3)
-/* a launch whose block exceeds the kernel's __launch_bounds__: refused on the host, before the launch (r06) */
+/* a launch whose block exceeds the kernel's __launch_bounds__: refused on the host, before the launch (r06).
+ * An entry point that issues several launches may already have enqueued its earlier stages when a later
+ * one is refused: after this status the call's outputs and workspace are undefined. */
 #define MSL_ERR_LAUNCH (-4)
 
 int msl_abi_version(void);

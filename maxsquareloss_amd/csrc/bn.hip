@@ -840,13 +840,18 @@ constexpr int kBnJointPair = 1;
 constexpr bool kBnJoint16Fwd = true;
 constexpr bool kBnJoint16Bwd = false;
 constexpr int kBnJointMaxC = 256;
-template <typename K, typename A>
-static int bn_launch_fused(K k4, K k9, K k16, K k33, K j4, K j9, K j16, int c, int p, hipStream_t st, const A& a) {
+// (one MSL_LAUNCH per kernel: each is checked against its own launch bound)
+template <auto K4, auto K9, auto K16, auto K33, auto J4, auto J9, auto J16, typename A>
+static int bn_launch_fused(int c, int p, hipStream_t st, const A& a) {
   const bool joint = kBnJointPair && a.NI == 2 && c <= kBnJointMaxC;
-  K k = p <= 4 * kBnFusedThreads ? (joint ? j4 : k4)
-        : p <= 9 * kBnFusedThreads ? (joint ? j9 : k9)
-        : p <= 16 * kBnFusedThreads ? (joint ? j16 : k16) : k33;
-  MSL_LAUNCH(k, dim3(c), dim3(kBnFusedThreads), 0, st, a);
+  const dim3 grid(c), block(kBnFusedThreads);
+  if (p > 16 * kBnFusedThreads) MSL_LAUNCH(K33, grid, block, 0, st, a);
+  else if (p <= 4 * kBnFusedThreads && joint) MSL_LAUNCH(J4, grid, block, 0, st, a);
+  else if (p <= 4 * kBnFusedThreads) MSL_LAUNCH(K4, grid, block, 0, st, a);
+  else if (p <= 9 * kBnFusedThreads && joint) MSL_LAUNCH(J9, grid, block, 0, st, a);
+  else if (p <= 9 * kBnFusedThreads) MSL_LAUNCH(K9, grid, block, 0, st, a);
+  else if (joint) MSL_LAUNCH(J16, grid, block, 0, st, a);
+  else MSL_LAUNCH(K16, grid, block, 0, st, a);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }
@@ -944,9 +949,9 @@ int msl_bn_fwd_mask(const float* x, const float* gamma, const float* beta, const
   a.momentum = momentum;
   a.absmax = absmax;
   a.mask = reinterpret_cast<unsigned long long*>(relu_mask);
-  if (fused) return bn_launch_fused(k_bn_fwd_fused<4>, k_bn_fwd_fused<9>, k_bn_fwd_fused<16>, k_bn_fwd_fused<33>,
-                                        k_bn_fwd_fused<4, true>, k_bn_fwd_fused<9, true>, k_bn_fwd_fused<16, kBnJoint16Fwd>, c, p, st,
-                                        a);
+  if (fused)
+    return bn_launch_fused<k_bn_fwd_fused<4>, k_bn_fwd_fused<9>, k_bn_fwd_fused<16>, k_bn_fwd_fused<33>,
+                           k_bn_fwd_fused<4, true>, k_bn_fwd_fused<9, true>, k_bn_fwd_fused<16, kBnJoint16Fwd>>(c, p, st, a);
   const unsigned blocks = (unsigned)cdiv((long long)R * p, (long long)a.chunk);
   if (vec)
     MSL_LAUNCH(k_bn_apply<true>, dim3(blocks), dim3(256), 0, st, a);
@@ -1013,8 +1018,8 @@ static int bn_bwd(const float* dy, const float* x, const float* y, const uint64_
   a.absmax = absmax_dx;
   a.mask = reinterpret_cast<const unsigned long long*>(relu_mask);
   if (fused)
-    return bn_launch_fused(k_bn_bwd_fused<4>, k_bn_bwd_fused<9>, k_bn_bwd_fused<16>, k_bn_bwd_fused<33>,
-                           k_bn_bwd_fused<4, true>, k_bn_bwd_fused<9, true>, k_bn_bwd_fused<16, kBnJoint16Bwd>, c, p, st, a);
+    return bn_launch_fused<k_bn_bwd_fused<4>, k_bn_bwd_fused<9>, k_bn_bwd_fused<16>, k_bn_bwd_fused<33>,
+                           k_bn_bwd_fused<4, true>, k_bn_bwd_fused<9, true>, k_bn_bwd_fused<16, kBnJoint16Bwd>>(c, p, st, a);
   const bool vec = al16(dy) && al16(x) && (!relu || al16(y)) && (!dx || al16(dx)) && (!dres || al16(dres));
   const unsigned blocks = (unsigned)cdiv((long long)R * p, (long long)a.chunk);
   if (vec) {

@@ -1,7 +1,9 @@
-// Dilated 3x3 convolution (stride 1, padding = dilation) as FP32-MFMA implicit
-// GEMMs on gfx950.  Replaces the cuDNN/oneDNN convolutions of
+// Dilated 3x3 (stride 1, padding = dilation) and pointwise convolutions as implicit GEMMs on the
+// gfx950 matrix cores: this file is their host half (packs, call records, plans, launches, the C entry
+// points); the GEMM kernels are in dconv_kernels.h.  Replaces the cuDNN/oneDNN convolutions of
 //   - Bottleneck.conv2 in layer3 (d=2) and layer4 (d=4)   deeplab_multi.py:17-18, 82-83
 //   - the live ASPP branches conv_d6 + conv_d12 (+bias)    deeplab_multi.py:51-66, 84-85
+//   - every 1x1 conv and, through im2col (stem.hip), the stem
 // forward, data gradient and weight gradient.
 //
 // Layout: activations are [C][P] fp32 with P = H*W (N = 1, NCHW).  The pixel
@@ -10,7 +12,8 @@
 // is then a constant shift of the linear pixel index plus a per-pixel validity
 // test (row wrap / image border), evaluated once per K-step per thread.
 //
-// GEMM mapping (MFMA v_mfma_f32_32x32x2_f32: exact f32 FMA chains):
+// GEMM mapping (one mapping, several matrix-core forms: exact-f32 v_mfma_f32_32x32x2_f32, bf16, the
+// fp32-accurate bf16x6 and f16x3 splits, fp16 - chosen per call by plan_fwd / plan_wgrad below):
 //   forward / dgrad:  C[m][p] = sum_k A[k][m] * B[k][p]
 //       k = ((branch*9 + tap)*ncb + cb)*16 + ci_local  (one tap, 16 channels per K-step;
 //       tap-major, so the shifted-pixel offsets change only every ncb K-steps)
@@ -18,10 +21,12 @@
 //       B = image[cb*16 + ci_local][p + shift(tap)]  (zero outside the image)
 //   wgrad (one GEMM per tap, batched over grid.z):
 //       dW[m][n][tap] = sum_p dY[m][p] * X[n][p + shift(tap)]   (K = pixels)
-// Both operands are staged through LDS ([k][m] / [k][n], so every MFMA operand
-// read is a conflict-free ds_read_b32 of 32 consecutive floats), double
-// buffered, one barrier per K-step.  Small GEMMs are split along K into fp32
-// slabs that a reduce kernel sums deterministically (fixed order).
+// The forward form runs stream-K over persistent workgroups (pieces of split tiles summed by
+// k_sk_reduce in a fixed order).  The exact-f32 and bf16 kernels stage both operands through LDS
+// ([k][m] / [k][n]: every MFMA operand read is a conflict-free ds_read_b32 of 32 consecutive floats);
+// the split forms read their weights from planes split at pack time and, for the 3x3 shapes, the image
+// operand straight to registers (BD) or pre-split (BP).  Only an odd K-step count with M <= 32 still
+// runs the split-K tile kernel, its fp32 slabs summed by k_reduce_slabs.
 #include "dconv_kernels.h"
 
 namespace msl {
@@ -259,11 +264,74 @@ __global__ void __launch_bounds__(256) k_pack_split_many(const msl_pack_job* __r
   }
 }
 
-// ---------------------------------------------------------------- planning
+// ---------------------------------------------------------------- the calls
+// The geometry of a conv call: nbranch dilated 3x3 branches over nimg images of h x w stacked along the
+// pixel axis (P = nimg * h * w), or one unshifted tap (dilation 0) over p flat pixels
+struct ConvGeom {
+  int nbranch, taps, h, w, nimg, dil0, dil1;
+};
+static ConvGeom geom_3x3(int nbranch, int h, int w, int nimg, int dil0, int dil1) {
+  return {nbranch, 9, h, w, nimg, dil0, dil1};
+}
+static ConvGeom geom_1x1(int p) { return {1, 1, 1, p, 1, 0, 0}; }
+
+// One forward-form GEMM (a forward or a data gradient): out[M][P] (=|+=) W . img
+struct FwdCall {
+  ConvGeom g;
+  const float* img;     // [cimg][P]: x (cin channels) forward, dy (cout channels) for a data gradient
+  const float* packed;  // the weights packed for this orientation (pack())
+  const float* bias;    // [nbranch][M] or null
+  float* out;           // [M][P]
+  int M, cimg;
+  int accum;            // out += the result (the fused residual-gradient sum)
+  const float* img_part;  // the caller's absmax partials of img (null: reduced here where the form scales)
+  int img_npart;
+  // with accum: out = mask(res) + the result (FwdArgs::accres, msl_pconv_dgrad_resmask*)
+  const float* res;
+  const unsigned long long* res_mask;
+  int res_nimg;
+};
+
+// One weight gradient: dw[nbranch][cout][cin][taps] (=|+=) dy . x^T over the P pixels
+struct WgradCall {
+  ConvGeom g;
+  const float* x;
+  const float* dy;
+  float* dw;
+  float* dbias;  // [nbranch][cout] or null
+  int cin, cout, accumulate;
+  // the caller's per-row absmax partials of x / dy (null: reduced here where the form scales)
+  const float* x_part;
+  int x_npart;
+  const float* dy_part;
+  int dy_npart;
+};
+
+static bool bad_dims(int nbranch, int cin, int cout, int h, int w, int nimg = 1) {
+  return nbranch < 1 || nbranch > 2 || cin < 1 || cout < 1 || h < 1 || w < 1 || nimg < 1 ||
+         (long long)nimg * h * w > (1LL << 30);
+}
+static bool bad_geom(const ConvGeom& g, int cin, int cout) {
+  return bad_dims(g.nbranch, cin, cout, g.h, g.w, g.nimg) ||
+         (g.taps == 9 && (g.dil0 < 1 || (g.nbranch == 2 && g.dil1 < 1)));
+}
+static bool bad_parts(const float* p, int n) { return p && n < 1; }
+
+// The argument checks of every forward-form / weight-gradient entry point (MSL_ERR_ARG)
+static bool bad_fwd(const FwdCall& c) {
+  return bad_geom(c.g, c.cimg, c.M) || !c.img || !c.packed || !c.out || bad_parts(c.img_part, c.img_npart) ||
+         (c.res && (!c.accum || !c.res_mask || c.res_nimg < 1 || (c.g.nimg * c.g.h * c.g.w) % c.res_nimg != 0));
+}
+static bool bad_wgrad(const WgradCall& c) {
+  return bad_geom(c.g, c.cin, c.cout) || !c.x || !c.dy || !c.dw || bad_parts(c.x_part, c.x_npart) ||
+         bad_parts(c.dy_part, c.dy_npart);
+}
+
+// ---------------------------------------------------------------- forward form: the plan
 // Forward form (fwd and dgrad) runs stream-K (k_igemm_fwd_sk): 128-pixel tiles of 128, 64 or
-// 32 rows (by M: the ASPP forward has 19 classes), two K-steps per LDS stage, up to 512
-// persistent workgroups (2 per CU), so every CU gets the same number of MFMA stages whatever
-// the tile count.  The split-K tile kernel remains for an odd K-step count with M <= 32.
+// 32 rows (by M: the ASPP forward has 19 classes), up to 512 persistent workgroups (2 per CU), so
+// every CU gets the same number of MFMA stages whatever the tile count.  The split-K tile kernel
+// remains for an odd K-step count with M <= 32.
 constexpr int kSkBN = 128, kSkNW = 512;
 // The call's forms (msl_forms, r05: per call, no process state): sk_hybrid = the forward-form
 // schedule (1: data-parallel rounds + stream-K remainder when the tiles outnumber the workers,
@@ -274,11 +342,29 @@ constexpr int kSkBN = 128, kSkNW = 512;
 // MFMAs per slice; dconv_kernels.h Split2h); packs are form-specific.
 static_assert(kMathF32 == 0 && kMathX6 == 2 && kMathH3P == 5, "msl_forms.f32_form values");
 
+// How the image operand reaches the MFMAs: staged through LDS; straight to registers (BD: dword pieces
+// of the shifted 3x3 rows, split in the loop); or pre-split once for the whole GEMM by k_split_img (BP)
+enum { kBLds = 0, kBDirect = 1, kBPre = 2 };
+
+// One instantiation of the stream-K kernel: the template arguments of k_igemm_fwd_sk / k_igemm_fwd_sk2
+struct SkForm {
+  int bm, G, stages, wm, wn;  // tile rows, K-steps per LDS stage, stages, wave layout
+  bool pw;                    // pointwise B rows (dwordx4 pieces)
+  int mt;                     // the kernel's math (kMathF32, kMathBf16, kMathX6P, kMathH3P, kMathH1P)
+  bool acc;                   // the accumulate epilogue
+  int bform;                  // kBLds / kBDirect / kBPre
+};
+static bool operator==(const SkForm& a, const SkForm& b) {
+  return a.bm == b.bm && a.G == b.G && a.stages == b.stages && a.wm == b.wm && a.wn == b.wn && a.pw == b.pw &&
+         a.mt == b.mt && a.acc == b.acc && a.bform == b.bform;
+}
+
 struct FwdPlan {
-  bool sk;
-  int G;  // stream-K: K-steps per stage
-  int bm, bn, bk, tiles_m, tiles_n, ksteps, kps, S;
-  int bmx;  // r06: the f16x3 pointwise GEMM's wide-tile rows (256; 0 = none), its pieces sized for them
+  bool sk;      // stream-K (form, sched); else the split-K tile kernel k_igemm_fwd (S slabs of kps K-steps)
+  SkForm form;
+  int tiles_m, tiles_n, ksteps, kps, S;
+  SkArgs sched;  // tiles, stages per tile, tdp / gm / NW / T (no pointers)
+  bool reduce;   // k_sk_reduce<form.bm> follows over the split tiles
 };
 
 // r06: f16x3 pointwise GEMMs with M a multiple of 256 from kPw256MinM on 256 x 128 tiles, 1 x 4 waves (each 256 rows
@@ -300,35 +386,298 @@ static int choose_split(int tiles, int ksteps, int min_steps) {
   return S;
 }
 
-static FwdPlan plan_fwd(int nbranch, int taps, int cimg, int M, int P, bool has_bias) {
-  FwdPlan pl;
-  const int groups = nbranch * cdiv(cimg, kCB) * taps;
+// The f16x3 / fp16 forward-form GEMMs that read their image operand pre-split (k_split_img, BP form):
+// the 3x3 ones with M >= 512: the split pass is shared by 4 row blocks and 9 taps (layer4 fwd 162 vs 174 us,
+// dgrad 172 vs 185; loses where the pass is a large share: pointwise 39 vs 31 us, layer2 34 vs 31, ASPP
+// 144 vs 135 - profiles/r03_bp_ab.txt); fp16 math (one plane: a quarter of the loads' instructions, half
+// their bytes) from M >= 128 (r05)
+static bool bp_form(int taps, int M, bool h1) { return taps == 9 && (M >= 512 || (h1 && M >= 128)); }
+
+// The stream-K schedule of tiles_m x tiles_n tiles of KS stages over at most nw_max workers.
+// At least as many tiles as workers: whole rounds of tiles data-parallel, stream-K over the rest
+// (SkArgs); fewer: pure stream-K.  Every stream-K worker must own at least one iteration: the piece
+// count of a tile is the number of workgroups its iteration range touches.
+static SkArgs plan_sk(int tiles_m, int tiles_n, int KS, int nw_max, int hybrid) {
+  SkArgs sk{};
+  sk.tiles_m = tiles_m;
+  sk.tiles_n = tiles_n;
+  sk.KS = KS;
+  const long long tiles = (long long)tiles_m * tiles_n;
+  sk.tdp = (hybrid && tiles >= nw_max) ? (int)(tiles / nw_max * nw_max) : 0;
+  // Tile order (r04): m fastest when whole rounds of tiles run data-parallel (hybrid): one XCD's
+  // workers then hold every m-block of a few pixel blocks, so each image block is fetched once and
+  // re-read from that L2 (same box: 256 -> 1024 fwd 42.7 vs 49.8 us, 2048 -> 512 dgrad 127 vs 141,
+  // layer4 fwd 214 vs 226; profiles/r04_tile_order_ab.txt).  n fastest for pure stream-K: a worker's
+  // range there is under one tile, the m-blocks of a pixel block run at staggered K offsets and get no
+  // L2 reuse, and the shared weights of n fastest win (ASPP fwd, M = 342 over 128 K-steps: 134 vs
+  // 101 us m fastest; layer3 fwd 79 vs 77.7; profiles/r04_aspp_tile_order.txt).
+  sk.gm = sk.tdp > 0 ? tiles_m : 1;
+  const long long T = (tiles - sk.tdp) * KS;
+  sk.NW = (int)std::min<long long>(nw_max, T);
+  // the remainder after data-parallel rounds (e.g. 16 tiles x 16 K-steps of a 256 -> 1024 pointwise
+  // GEMM): at one or two K-steps per worker every worker writes a whole 64-KB piece for almost no
+  // work; at least kSkMinIt K-steps each (512 -> 2048 fwd 75.9 vs 82.2 us, 2048 -> 512 dgrad 85.6 vs
+  // 90.0)
+  constexpr long long kSkMinIt = 8;
+  if (sk.tdp > 0) sk.NW = (int)std::max<long long>(1, std::min<long long>(sk.NW, T / kSkMinIt));
+  sk.T = (int)T;
+  return sk;
+}
+
+// Every form decision of a forward-form call; `math` = the entry point's (kMathF32 / kMathX6 / kMathH3P: the
+// fp32 entry points' f32_form; kMathBf16; kMathH1P = fp16).  No launches, no pointers.
+static FwdPlan plan_fwd(int math, int nbranch, int taps, int cimg, int M, int P, int accum, int dil0,
+                        const msl_forms* forms) {
+  FwdPlan pl{};
+  const bool f16 = math == kMathH3P || math == kMathH1P;
+  const int groups = nbranch * cdiv(cimg, kCB) * taps;  // K-steps: one tap, 16 channels each
   const int bm = M > 64 ? 128 : (M > 32 ? 64 : 32);
+  pl.ksteps = groups;
+  pl.tiles_n = cdiv(P, kSkBN);
   pl.sk = groups % 2 == 0 || bm > 32;
-  pl.bmx = pl.sk ? wide_rows(taps, M) : 0;
-  if (pl.sk) {
-    pl.G = groups % 2 == 0 ? 2 : 1;
-    pl.bm = bm;
-    pl.bn = kSkBN;
-    pl.bk = pl.G * kCB;
-    pl.tiles_m = cdiv(M, pl.bm);
-    pl.tiles_n = cdiv(P, pl.bn);
-    pl.ksteps = groups;
-    pl.kps = groups / pl.G;  // stages per tile
-    pl.S = 1;
+  if (!pl.sk) {  // k_igemm_fwd<64, 128, 16, 2, 2>: exact f32 in every math, S slabs summed by k_reduce_slabs
+    pl.tiles_m = cdiv(M, 64);
+    const int S = choose_split(pl.tiles_m * pl.tiles_n, groups, 4);
+    pl.kps = cdiv(groups, S);
+    pl.S = cdiv(groups, pl.kps);
     return pl;
   }
-  pl.G = 1;
-  pl.bm = 64;
-  pl.bn = 128;
-  pl.bk = 16;
-  pl.tiles_m = cdiv(M, pl.bm);
-  pl.tiles_n = cdiv(P, pl.bn);
-  pl.ksteps = groups;
-  int S = choose_split(pl.tiles_m * pl.tiles_n, pl.ksteps, 4);
-  pl.kps = cdiv(pl.ksteps, S);
-  pl.S = cdiv(pl.ksteps, pl.kps);
+  // exact-f32 / bf16 MFMA, both operands through LDS: two K-steps per stage where the count is even, 2 x 2
+  // waves (1 x 4 on the 32-row tiles); also the 64- and 32-row tiles of the x6 form (no gain measured there)
+  SkForm& f = pl.form;
+  f.bm = bm;
+  f.G = groups % 2 == 0 ? 2 : 1;
+  f.stages = f.G == 2 ? 2 : 3;
+  f.wm = bm == 32 ? 1 : 2;
+  f.wn = bm == 32 ? 4 : 2;
+  f.mt = math == kMathBf16 ? kMathBf16 : kMathF32;
+  f.acc = accum != 0;
+  if (math == kMathX6 && bm == 128) {
+    // one K-step per stage, four stages deep (r01 tuning harness, layer3: 87 us vs 115 with two K-steps
+    // per stage), the weights from the bf16 planes that pack() split once (M > 64 <=> 128-row tiles)
+    f.G = 1;
+    f.stages = 4;
+    f.mt = kMathX6P;
+  } else if (f16) {
+    // f16x3 / fp16 (which reads the f16x3 packs' hi planes): one K-step per stage, four stages, the weights
+    // from the fp16 planes.  Waves 1 x 4 (each 128 rows x 32 pixels): every wave splits only its own B columns
+    // (2 x 2 waves split each column twice); step 40.5 vs 40.9 ms on one box (profiles/r02_f16x3_waves.txt)
+    f.G = 1;
+    f.stages = 4;
+    f.wm = 1;
+    f.wn = 4;
+    f.mt = math;
+    // the image operand straight to registers (BD form) for the shifted 3x3 rows (dword pieces); the pointwise
+    // rows keep their two dwordx4 LDS-DMA pieces per wave and K-step (BD loses there: 256 -> 1024 fwd 32.7 vs
+    // 31.0 us, 2048 -> 512 82.7 vs 75.1; layer3 3x3 fwd 52.4 vs 55.0, layer4 172 vs 190;
+    // profiles/r03_fwd_forms_ab.txt).  Full 16-channel blocks only: the stem's 147-row im2col operand keeps
+    // the LDS form
+    const bool bd = cimg % kCB == 0;
+    if (bm <= 64) {
+      // r03: M <= 64 (the 19-class ASPP forward, layer1's 64-channel 3x3 and 256 -> 64 convs, the 64-channel
+      // data gradients, the stem's 147 -> 64) on 64-row tiles of the same kernel, pointwise too (one unshifted
+      // tap), instead of exact-f32 32 / 64-row tiles: 3 fp16 MFMAs per 16-deep slice at 64 rows cost 2.7x less
+      // matrix time than 8 f32 MFMAs at 32 rows.  r04: the fp16 math too (fwd_sk_body AHALF).  The only
+      // accumulating BD form: the pointwise M <= 64 data gradients
+      f.bm = 64;
+      f.bform = bd ? kBDirect : kBLds;
+    } else if (taps == 1 && dil0 == 0) {
+      // pointwise: B rows are unshifted, so they move as dwordx4 (4 pixels per lane: 2 DMAs per wave and
+      // K-step instead of 8 dword ones): 1-4 us per call on the wide 1x1 GEMMs (profiles/r02_f16x3_pw_dma.txt)
+      f.pw = true;
+      if (math == kMathH3P && wide_rows(taps, M)) {
+        f.bm = 256;
+        f.stages = 3;
+      } else if (math == kMathH1P && groups % 2 == 0) {
+        // fp16 (r04): two K-steps per LDS stage, three stages (72 KB, two workgroups per CU): one barrier per
+        // 8 MFMAs per wave instead of 4 (f16x3's two planes would need 96 KB)
+        f.G = 2;
+        f.stages = 3;
+      }
+    } else if (!f.acc) {  // (no 3x3 call accumulates; the 128-row accumulating BD / BP forms are not instantiated)
+      f.bform = bp_form(taps, M, math == kMathH1P) ? kBPre : bd ? kBDirect : kBLds;
+    }
+  }
+  pl.tiles_m = cdiv(M, f.bm);
+  pl.kps = groups / f.G;  // stages per tile
+  pl.S = 1;
+  pl.sched = plan_sk(pl.tiles_m, pl.tiles_n, pl.kps, kSkNW, forms_of(forms).sk_hybrid);
+  pl.reduce = pl.sched.T > 0;
   return pl;
+}
+
+// Workspace of a forward-form call: the stream-K pieces, NW x 2 x BM*BN floats (summed by k_sk_reduce; no
+// flags or other state survive a call), then (the BP form) the image operand's fp16 planes, then (f16x3)
+// the image's kNPart absmax partials at the end of the caller's workspace.  Independent of the call's
+// forms and math (they come with the call, not with the query): the pieces sized for the largest tile the
+// shape can get (64 rows at M <= 64, the 256-row pointwise tiles twice the 128-row pieces - r05's 256 /
+// 384-row attempt kept the 128-row size, and its pieces ran past the workspace into the partials behind
+// them), and a 3x3 GEMM with 128 <= M < 512 reserves the image planes that only the fp16 math's BP form
+// reads (cimg x P x 4 bytes, e.g. ~17 MB at layer2's pair shape): conservative, accepted.
+// The stem / pointwise calls reserve no planes.
+constexpr size_t kPartBytes = kNPart * sizeof(float);
+static size_t fwd_piece_bytes(int taps, int M) {
+  return align_up((size_t)kSkNW * 2 * std::max(wide_rows(taps, M), M > 64 ? 128 : 64) * kSkBN * sizeof(float), 256);
+}
+static size_t img_planes_bytes(int cimg, int P) { return align_up((size_t)cdiv(cimg, kCB) * kCB * P * 4, 256); }
+static size_t fwd_ws_bytes(const FwdPlan& pl, int taps, int cimg, int M, int P) {
+  if (pl.sk) return fwd_piece_bytes(taps, M) + (bp_form(taps, M, true) ? img_planes_bytes(cimg, P) : 0) + kPartBytes;
+  return (pl.S > 1 ? (size_t)pl.S * M * P * sizeof(float) : 0) + kPartBytes;
+}
+static size_t fwd_query_bytes(int nbranch, int taps, int cimg, int M, int P) {
+  return fwd_ws_bytes(plan_fwd(kMathF32, nbranch, taps, cimg, M, P, 0, taps == 9, nullptr), taps, cimg, M, P);
+}
+static float* ws_partials(void* ws, size_t ws_bytes, int k) {  // k-th partials block from the end
+  return reinterpret_cast<float*>((char*)ws + ((ws_bytes - (size_t)k * kPartBytes) & ~(size_t)15));
+}
+
+// ---------------------------------------------------------------- forward form: the kernels
+// Every instantiation of the stream-K kernel, keyed by its own template arguments, with its launch bound
+// (MSL_LAUNCH_ENTRY).  k_igemm_fwd_sk2 is the same kernel held to two waves per SIMD (the f16 forms).  A
+// plan whose form has no row here is MSL_ERR_SHAPE.
+struct SkKernel {
+  SkForm form;
+  void (*fn)(FwdArgs, SkArgs);
+  std::atomic<int> bound{0};
+};
+#define MSL_SK(BM, G, ST, WM, WN, MT, ACC) \
+  {{BM, G, ST, WM, WN, false, MT, ACC, kBLds}, k_igemm_fwd_sk<BM, kSkBN, G, ST, WM, WN, false, MT, ACC>}
+#define MSL_SK_BOTH(BM, G, ST, WM, WN, MT) MSL_SK(BM, G, ST, WM, WN, MT, false), MSL_SK(BM, G, ST, WM, WN, MT, true)
+#define MSL_SK2(BM, G, ST, PW, MT, ACC, BF)  \
+  {{BM, G, ST, 1, 4, PW, MT, ACC, BF},       \
+   k_igemm_fwd_sk2<BM, kSkBN, G, ST, 1, 4, PW, MT, ACC, (BF) != kBLds, (BF) == kBPre>}
+#define MSL_SK2_BOTH(BM, G, ST, PW, MT, BF) MSL_SK2(BM, G, ST, PW, MT, false, BF), MSL_SK2(BM, G, ST, PW, MT, true, BF)
+// the f16x3 / fp16 rows they share: 64-row tiles in every operand form, 128-row 3x3 and pointwise tiles
+#define MSL_SK2_F16(MT)                                                                                      \
+  MSL_SK2_BOTH(64, 1, 4, false, MT, kBLds), MSL_SK2_BOTH(64, 1, 4, false, MT, kBDirect),                      \
+  MSL_SK2_BOTH(64, 1, 4, false, MT, kBPre), /* (64-row BP: built since r03, chosen by no plan) */             \
+  MSL_SK2_BOTH(128, 1, 4, false, MT, kBLds), MSL_SK2(128, 1, 4, false, MT, false, kBDirect),                  \
+  MSL_SK2(128, 1, 4, false, MT, false, kBPre), MSL_SK2_BOTH(128, 1, 4, true, MT, kBLds)
+static SkKernel kSkKernels[] = {
+    MSL_SK_BOTH(128, 2, 2, 2, 2, kMathF32), MSL_SK_BOTH(128, 1, 3, 2, 2, kMathF32),
+    MSL_SK_BOTH(64, 2, 2, 2, 2, kMathF32), MSL_SK_BOTH(64, 1, 3, 2, 2, kMathF32),
+    MSL_SK_BOTH(32, 2, 2, 1, 4, kMathF32),
+    MSL_SK_BOTH(128, 2, 2, 2, 2, kMathBf16), MSL_SK_BOTH(128, 1, 3, 2, 2, kMathBf16),
+    MSL_SK_BOTH(64, 2, 2, 2, 2, kMathBf16), MSL_SK_BOTH(64, 1, 3, 2, 2, kMathBf16),
+    MSL_SK_BOTH(32, 2, 2, 1, 4, kMathBf16),
+    // (the in-loop bf16x6 split: built since r01, chosen by no plan since the x6 form reads pre-split weights)
+    MSL_SK_BOTH(128, 2, 2, 2, 2, kMathX6), MSL_SK_BOTH(128, 1, 3, 2, 2, kMathX6),
+    MSL_SK_BOTH(128, 1, 4, 2, 2, kMathX6P),
+    MSL_SK2_F16(kMathH3P), MSL_SK2_BOTH(256, 1, 3, true, kMathH3P, kBLds),
+    MSL_SK2_F16(kMathH1P), MSL_SK2_BOTH(128, 2, 3, true, kMathH1P, kBLds),
+};
+#undef MSL_SK2_F16
+#undef MSL_SK2_BOTH
+#undef MSL_SK2
+#undef MSL_SK_BOTH
+#undef MSL_SK
+
+static SkKernel* sk_kernel(const SkForm& f) {
+  for (SkKernel& k : kSkKernels)
+    if (k.form == f) return &k;
+  return nullptr;
+}
+
+// Plan, then launch in this order: k_absmax, k_split_img, the GEMM, k_sk_reduce
+static int launch_fwd_form(int math, const FwdCall& c, const msl_forms* forms, void* ws, size_t ws_bytes,
+                           hipStream_t st) {
+  const ConvGeom& g = c.g;
+  const int P = g.nimg * g.h * g.w;
+  const FwdPlan pl = plan_fwd(math, g.nbranch, g.taps, c.cimg, c.M, P, c.accum, g.dil0, forms);
+  if (ws_bytes < fwd_ws_bytes(pl, g.taps, c.cimg, c.M, P)) return MSL_ERR_WORKSPACE;
+  FwdArgs a{};
+  a.A = c.packed;
+  a.B = c.img;
+  a.C = c.out;
+  a.bias = c.bias;
+  a.nbias = g.nbranch;  // (read with a bias only)
+  a.M = c.M;
+  a.lda = pad_to(c.M, kPackPad);
+  a.H = g.h;
+  a.W = g.w;
+  a.P = P;
+  a.cimg = c.cimg;
+  a.ncb = cdiv(c.cimg, kCB);
+  a.dil0 = g.dil0;
+  a.dil1 = g.dil1;
+  a.ksteps = pl.ksteps;
+  a.kps = pl.kps;
+  a.taps = g.taps;
+  a.slab = (long long)c.M * P;
+  a.accum = c.accum;
+  a.accres = c.res;
+  a.accmask = c.res_mask;
+  a.accni = c.res_nimg;
+  const dim3 block(256);
+  if (!pl.sk) {
+    // the split-K tile kernel (odd K-step count, M <= 32) has no bf16 form and no accumulate epilogue
+    if (math == kMathBf16 || c.accum) return MSL_ERR_SHAPE;
+    if (pl.S > 1) {
+      a.C = (float*)ws;
+      a.bias = nullptr;
+    }
+    MSL_LAUNCH((k_igemm_fwd<64, 128, 16, 2, 2>), dim3(pl.tiles_n, pl.tiles_m, pl.S), block, 0, st, a);
+    MSL_CHECK_LAUNCH();
+    if (pl.S > 1) {
+      const long long n = (long long)c.M * P;
+      const int blocks = (int)std::min<long long>(cdiv(n, 256), 4096);
+      MSL_LAUNCH(k_reduce_slabs, dim3(blocks), block, 0, st, (const float*)ws, pl.S, n, c.out, 0, c.bias, a.nbias, c.M,
+                 P);
+      MSL_CHECK_LAUNCH();
+    }
+    return MSL_OK;
+  }
+  const SkForm& f = pl.form;
+  // 32-bit index arithmetic in the kernel (the bound of 128-row tiles, for the 256-row ones too)
+  if ((long long)cdiv(c.M, std::min(f.bm, 128)) * pl.tiles_n * pl.kps * kSkNW >= (1LL << 31) ||
+      (long long)c.cimg * P >= (1LL << 29) || (long long)pl.ksteps * kCB * a.lda >= (1LL << 29))
+    return MSL_ERR_SHAPE;
+  SkKernel* k = sk_kernel(f);
+  if (!k) return MSL_ERR_SHAPE;
+  SkArgs sk = pl.sched;
+  sk.part = (float*)ws;
+  const long long tiles = (long long)pl.tiles_m * pl.tiles_n;
+  const dim3 grid(sk.tdp > 0 ? kSkNW : sk.NW), rgrid(f.bm * kSkBN / 1024, (unsigned)(tiles - sk.tdp));
+  const bool f16 = f.mt == kMathH3P || f.mt == kMathH1P;
+  if (f16 || f.mt == kMathX6P) {  // the weights' planes, behind the fp32 part of the pack
+    const long long f32 = (long long)pl.ksteps * kCB * a.lda;
+    a.Ax6 = reinterpret_cast<const __bf16*>(c.packed + f32);
+    if (f16) a.ascale = c.packed + pack_tail_offset(f32) + kNPart;  // the pack's {sA, 1/sA}
+  }
+  if (f16) {  // the image's absmax partials: the caller's (msl_absmax_partials, a BN kernel) or k_absmax's
+    a.bpart = c.img_part;
+    a.bnpart = c.img_npart;
+    if (!c.img_part) {
+      float* part = ws_partials(ws, ws_bytes, 1);
+      MSL_LAUNCH(k_absmax, dim3(kNPart), block, 0, st, c.img, (long long)c.cimg * P, 0LL, 1, part);
+      MSL_CHECK_LAUNCH();
+      a.bpart = part;
+      a.bnpart = kNPart;
+    }
+  }
+  if (f.bform == kBPre) {  // the image's fp16 planes, behind the pieces
+    f16x8* planes = reinterpret_cast<f16x8*>((char*)ws + fwd_piece_bytes(g.taps, c.M));
+    const long long n = (long long)a.ncb * 2 * P;
+    const dim3 sgrid((unsigned)std::min<long long>(cdiv(n, 256), 8192));
+    if (f.mt == kMathH1P)
+      MSL_LAUNCH(k_split_img<1>, sgrid, block, 0, st, c.img, c.cimg, a.ncb, P, a.bpart, a.bnpart, planes);
+    else
+      MSL_LAUNCH(k_split_img<2>, sgrid, block, 0, st, c.img, c.cimg, a.ncb, P, a.bpart, a.bnpart, planes);
+    MSL_CHECK_LAUNCH();
+    a.Bx6 = planes;
+  }
+  MSL_LAUNCH_ENTRY(k->fn, k->bound, grid, block, 0, st, a, sk);
+  MSL_CHECK_LAUNCH();
+  if (pl.reduce) {
+    switch (f.bm) {
+      case 32: MSL_LAUNCH((k_sk_reduce<32, kSkBN>), rgrid, block, 0, st, a, sk); break;
+      case 64: MSL_LAUNCH((k_sk_reduce<64, kSkBN>), rgrid, block, 0, st, a, sk); break;
+      case 128: MSL_LAUNCH((k_sk_reduce<128, kSkBN>), rgrid, block, 0, st, a, sk); break;
+      default: MSL_LAUNCH((k_sk_reduce<256, kSkBN>), rgrid, block, 0, st, a, sk); break;
+    }
+    MSL_CHECK_LAUNCH();
+  }
+  return MSL_OK;
 }
 
 // Weight gradient: stream-K over (tile, 64-pixel stage) (k_wgrad_sk + k_wsk_reduce).  Tiles by
@@ -416,352 +765,6 @@ static WgradPlan plan_wgrad(int nbranch, int taps, int cin, int cout, int P, boo
 static size_t wgrad_piece_bytes(const WgradPlan& pl) { return (size_t)pl.nw * pl.slots * pl.bm * pl.bn * sizeof(float); }
 // (+ two K-steps: k_wgrad_x6's loads one stage ahead read up to K-step KS + 1, unused)
 static size_t wgrad_planes_bytes(const WgradPlan& pl) { return pl.rx6 ? (size_t)(pl.KS + 2) * 6 * pl.lda * 16 : 0; }
-
-// stream-K workspace: the published pieces, NW x 2 x BM*BN floats (summed by k_sk_reduce; no
-// flags or other state survive a call).
-// + (f16x3) the image's kNPart absmax partials at the end of the caller's workspace.
-constexpr size_t kPartBytes = kNPart * sizeof(float);
-// stream-K pieces, then (the BP form) the image operand's fp16 planes, then the partials at the end
-static size_t fwd_piece_bytes(const FwdPlan& pl) {
-  // (the <= 64-row f16x3 / fp16 3x3 tiles run 64 rows: room for those pieces whatever the form; the 256-row
-  // pointwise tiles twice the 128-row pieces - r05's 256 / 384-row attempt kept the 128-row size, and its
-  // pieces ran past the workspace into the image partials behind them)
-  return align_up((size_t)kSkNW * 2 * std::max(pl.bmx, std::max(pl.bm, 64)) * pl.bn * sizeof(float), 256);
-}
-static size_t img_planes_bytes(int cimg, int P) { return align_up((size_t)cdiv(cimg, kCB) * kCB * P * 4, 256); }
-// The f16x3 / fp16 forward-form GEMMs that read their image operand pre-split (k_split_img, BP form):
-// the 3x3 ones with M >= 512 (profiles/r03_bp_ab.txt); fp16 math (one plane: a quarter of the loads'
-// instructions, half their bytes) from M >= 128 (r05)
-// r06: the 3x3 GEMMs with M >= kBqMinM read the pre-split image in the 2 x 2 wave layout (BQ: 64 rows x 64
-// pixels per wave, half the A-fragment LDS reads per MFMA of the 1 x 4 layout, no split in the loop)
-constexpr int kBqMinM = 1 << 30;
-static bool bq_form(int taps, int M, bool small_f16) { return taps == 9 && !small_f16 && M >= kBqMinM; }
-
-// The stream-K schedule of a forward-form launch over at most nw_max workers (see launch_fwd_form)
-static SkArgs plan_sk(int tiles_m, int tiles_n, int KS, int nw_max, int hybrid, float* part) {
-  SkArgs sk{};
-  sk.part = part;
-  sk.tiles_m = tiles_m;
-  sk.tiles_n = tiles_n;
-  sk.KS = KS;
-  const long long tiles = (long long)tiles_m * tiles_n;
-  sk.tdp = (hybrid && tiles >= nw_max) ? (int)(tiles / nw_max * nw_max) : 0;
-  sk.gm = sk.tdp > 0 ? tiles_m : 1;
-  const long long T = (tiles - sk.tdp) * KS;
-  sk.NW = (int)std::min<long long>(nw_max, T);
-  constexpr long long kSkMinIt = 8;
-  if (sk.tdp > 0) sk.NW = (int)std::max<long long>(1, std::min<long long>(sk.NW, T / kSkMinIt));
-  sk.T = (int)T;
-  return sk;
-}
-static bool bp_form(int taps, int M, bool small_f16, bool h1 = false) {
-  return taps == 9 && !small_f16 && (M >= 512 || (h1 && M >= 128) || bq_form(taps, M, small_f16));
-}
-static size_t fwd_ws_bytes(const FwdPlan& pl, int M, int P, int cimg, int taps) {
-  // the planes only where the BP form can run (the stem / pointwise calls reserved them too).  The
-  // query is form-independent (the forms come with the call, not with the query), so a 3x3 GEMM with
-  // 128 <= M < 512 reserves the image planes that only the fp16 math's BP form reads (cimg x P x 4 bytes, e.g.
-  // ~17 MB at layer2's pair shape) in every form: conservative, accepted
-  if (pl.sk) return fwd_piece_bytes(pl) + (bp_form(taps, M, false, true) ? img_planes_bytes(cimg, P) : 0) + kPartBytes;
-  return (pl.S > 1 ? (size_t)pl.S * M * P * sizeof(float) : 0) + kPartBytes;
-}
-static float* ws_partials(void* ws, size_t ws_bytes, int k) {  // k-th partials block from the end
-  return reinterpret_cast<float*>((char*)ws + ((ws_bytes - (size_t)k * kPartBytes) & ~(size_t)15));
-}
-
-// The forward-form kernel, plain or with the accumulate epilogue (a template form of its own)
-template <int BM, int G, int ST, int WM, int WN, int MT, bool PW = false>
-static int launch_sk(int accum, dim3 grid, dim3 block, hipStream_t st, const FwdArgs& a, const SkArgs& sk,
-                      bool bp = false) {
-  if constexpr (MT == kMathH3P || MT == kMathH1P) {  // held to two waves per SIMD (k_igemm_fwd_sk2)
-    if constexpr (!PW && BM == 128 && G == 1 && ST == 4 && WM == 2 && WN == 2) {
-      // the 2 x 2 pre-split form (BQ, r06): 3x3 GEMMs only, never accumulating
-      if (bp && !accum) {
-        MSL_LAUNCH((k_igemm_fwd_sk2<BM, kSkBN, G, ST, WM, WN, PW, MT, false, true, true>), grid, block, 0, st,
-                           a, sk);
-        return MSL_OK;
-      }
-    }
-    if constexpr (!PW && (BM == 128 || BM == 64) && G == 1 && ST == 4 && WM == 1 && WN == 4) {
-      // (accumulating BD / BP forms at 64 rows only: the pointwise M <= 64 data gradients; no 3x3 call
-      // accumulates, and the 128-row accumulating 3x3 forms are not instantiated)
-      if (bp) {  // the image operand pre-split by k_split_img (never for the pointwise kernels: no BP / BD form)
-        if constexpr (BM == 64) {
-          if (accum) {
-            MSL_LAUNCH((k_igemm_fwd_sk2<BM, kSkBN, G, ST, WM, WN, PW, MT, true, true, true>), grid, block, 0,
-                               st, a, sk);
-            return MSL_OK;
-          }
-        }
-        if (!accum) {
-          MSL_LAUNCH((k_igemm_fwd_sk2<BM, kSkBN, G, ST, WM, WN, PW, MT, false, true, true>), grid, block, 0,
-                             st, a, sk);
-          return MSL_OK;
-        }
-      }
-      // the image operand straight to registers (BD form) for the shifted 3x3 rows (dword pieces);
-      // the pointwise rows keep their two dwordx4 LDS-DMA pieces per wave and K-step (BD loses there:
-      // 256 -> 1024 fwd 32.7 vs 31.0 us, 2048 -> 512 82.7 vs 75.1; layer3 3x3 fwd 52.4 vs 55.0,
-      // layer4 172 vs 190; profiles/r03_fwd_forms_ab.txt)
-      // (full 16-channel blocks only: the stem's 147-row im2col operand keeps the LDS form)
-      if (a.cimg % kCB == 0) {
-        if constexpr (BM == 64) {
-          if (accum) {
-            MSL_LAUNCH((k_igemm_fwd_sk2<BM, kSkBN, G, ST, WM, WN, PW, MT, true, true>), grid, block, 0, st, a,
-                               sk);
-            return MSL_OK;
-          }
-        }
-        if (!accum) {
-          MSL_LAUNCH((k_igemm_fwd_sk2<BM, kSkBN, G, ST, WM, WN, PW, MT, false, true>), grid, block, 0, st, a,
-                             sk);
-          return MSL_OK;
-        }
-      }
-    }
-    if (accum)
-      MSL_LAUNCH((k_igemm_fwd_sk2<BM, kSkBN, G, ST, WM, WN, PW, MT, true>), grid, block, 0, st, a, sk);
-    else
-      MSL_LAUNCH((k_igemm_fwd_sk2<BM, kSkBN, G, ST, WM, WN, PW, MT, false>), grid, block, 0, st, a, sk);
-  } else {
-    if (accum)
-      MSL_LAUNCH((k_igemm_fwd_sk<BM, kSkBN, G, ST, WM, WN, false, MT, true>), grid, block, 0, st, a, sk);
-    else
-      MSL_LAUNCH((k_igemm_fwd_sk<BM, kSkBN, G, ST, WM, WN, false, MT, false>), grid, block, 0, st, a, sk);
-  }
-  return MSL_OK;
-}
-
-template <int MT>
-static int launch_fwd_form(const float* img, int cimg, const float* packed, int M, const float* bias,
-                           int nbias, float* out, int nbranch, int taps, int h, int w, int nimg, int dil0,
-                           int dil1, const msl_forms* forms, void* ws, size_t ws_bytes, hipStream_t st,
-                           int accum = 0, const float* img_part = nullptr, int img_npart = 0,
-                           const float* accres = nullptr, const unsigned long long* accmask = nullptr, int accni = 1) {
-  if (forms_bad(forms)) return MSL_ERR_ARG;
-  const int P = nimg * h * w;  // nimg images of h x w stacked along the pixel axis
-  FwdPlan pl = plan_fwd(nbranch, taps, cimg, M, P, bias != nullptr);
-  // The x6 form runs one K-step per stage, three stages deep (r01 tuning harness, layer3:
-  // 87 us vs 115 with two K-steps per stage; f32 is indifferent); its 64- and 32-row tiles stay
-  // on exact f32 MFMA (no gain measured there).
-  // split forms (and the fp16 math, which reads the f16x3 packs' hi planes): 128-row tiles only
-  constexpr bool F16 = MT == kMathH3P || MT == kMathH1P;
-  constexpr bool X6L = MT == kMathX6 || F16;
-  constexpr int MS = X6L ? kMathF32 : MT;
-  constexpr int MB = F16 ? kMathX6 : MT;       // (not reached by the split forms)
-  if (X6L && pl.sk && pl.bm == 128) {
-    pl.G = 1;
-    pl.bk = kCB;
-    pl.kps = pl.ksteps;
-  }
-  // f16x3 / fp16 (r03): the 3x3 / ASPP GEMMs with M <= 64 (the 19-class ASPP forward, layer1's
-  // 64-channel convs) on 64-row tiles of the same kernel (weights from the fp16 planes, the image
-  // operand straight to registers) instead of exact-f32 32 / 64-row tiles: 3 fp16 MFMAs per 16-deep
-  // slice at 64 rows cost 2.7x less matrix time than 8 f32 MFMAs at 32 rows.
-  // (r03: also the pointwise / stem GEMMs with M <= 64 - layer1's 256 -> 64 convs, the 64-channel data
-  // gradients, the stem's 147 -> 64 - through the same form with one unshifted tap)
-  // r04: the fp16 math too (its single fp16 plane split into half-wave A pieces, fwd_sk_body AHALF)
-  const bool small_f16 = F16 && pl.sk && pl.bm <= 64;
-  if (small_f16) {
-    pl.G = 1;
-    pl.bm = 64;
-    pl.bk = kCB;
-    pl.tiles_m = cdiv(M, 64);
-    pl.kps = pl.ksteps;
-  }
-  // fp16 pointwise GEMMs (r04): two K-steps per LDS stage, three stages (72 KB, two workgroups per
-  // CU): one barrier per 8 MFMAs per wave instead of 4 (f16x3's two planes would need 96 KB)
-  const bool pw2 = MT == kMathH1P && pl.sk && pl.bm == 128 && taps == 1 && dil0 == 0 && pl.ksteps % 2 == 0;
-  if (pw2) {
-    pl.G = 2;
-    pl.bk = 2 * kCB;
-    pl.kps = pl.ksteps / 2;
-  }
-  if (ws_bytes < fwd_ws_bytes(pl, M, P, cimg, taps)) return MSL_ERR_WORKSPACE;
-  FwdArgs a{};
-  a.Ax6 = nullptr;
-  a.ascale = nullptr;
-  a.bpart = nullptr;
-  a.bnpart = 0;
-  a.accum = accum;
-  a.accres = accres;  // (r06: the masked residual gradient of msl_pconv_dgrad_resmask*; needs accum)
-  a.accmask = accmask;
-  a.accni = accni;
-  if (accres && (!accum || !accmask || accni < 1 || P % accni != 0)) return MSL_ERR_ARG;
-  a.A = packed;
-  a.B = img;
-  a.C = pl.S > 1 ? (float*)ws : out;
-  a.bias = pl.S > 1 ? nullptr : bias;
-  a.nbias = nbias;
-  a.M = M;
-  a.lda = pad_to(M, kPackPad);
-  a.H = h;
-  a.W = w;
-  a.P = P;
-  a.cimg = cimg;
-  a.ncb = cdiv(cimg, kCB);
-  a.dil0 = dil0;
-  a.dil1 = dil1;
-  a.ksteps = pl.ksteps;
-  a.kps = pl.kps;
-  a.taps = taps;
-  a.slab = (long long)M * P;
-  if (pl.sk) {
-    SkArgs sk{};
-    sk.part = (float*)ws;
-    sk.tiles_m = pl.tiles_m;
-    sk.tiles_n = pl.tiles_n;
-    sk.KS = pl.kps;
-    const long long tiles = (long long)pl.tiles_m * pl.tiles_n;
-    if (tiles * sk.KS * kSkNW >= (1LL << 31) || (long long)cimg * P >= (1LL << 29) ||
-        (long long)pl.ksteps * kCB * a.lda >= (1LL << 29))
-      return MSL_ERR_SHAPE;  // 32-bit index arithmetic in the kernel
-    // at least as many tiles as workers: whole rounds of tiles data-parallel, stream-K over the
-    // rest (SkArgs); fewer: pure stream-K.  Every stream-K worker must own at least one iteration:
-    // the piece count of a tile is the number of workgroups its iteration range touches.
-    sk.tdp = (forms_of(forms).sk_hybrid && tiles >= kSkNW) ? (int)(tiles / kSkNW * kSkNW) : 0;
-    // Tile order (r04): m fastest when whole rounds of tiles run data-parallel (hybrid): one XCD's
-    // workers then hold every m-block of a few pixel blocks, so each image block is fetched once and
-    // re-read from that L2 (same box: 256 -> 1024 fwd 42.7 vs 49.8 us, 2048 -> 512 dgrad 127 vs 141,
-    // layer4 fwd 214 vs 226; profiles/r04_tile_order_ab.txt).  n fastest for pure stream-K: a worker's
-    // range there is under one tile, the m-blocks of a pixel block run at staggered K offsets and get no
-    // L2 reuse, and the shared weights of n fastest win (ASPP fwd, M = 342 over 128 K-steps: 134 vs
-    // 101 us m fastest; layer3 fwd 79 vs 77.7; profiles/r04_aspp_tile_order.txt).
-    sk.gm = sk.tdp > 0 ? pl.tiles_m : 1;
-    const long long T = (tiles - sk.tdp) * sk.KS;
-    sk.NW = (int)std::min<long long>(kSkNW, T);
-    // the remainder after data-parallel rounds (e.g. 16 tiles x 16 K-steps of a 256 -> 1024 pointwise
-    // GEMM): at one or two K-steps per worker every worker writes a whole 64-KB piece for almost no
-    // work; at least kSkMinIt K-steps each (512 -> 2048 fwd 75.9 vs 82.2 us, 2048 -> 512 dgrad 85.6 vs
-    // 90.0)
-    constexpr long long kSkMinIt = 8;
-    if (sk.tdp > 0) sk.NW = (int)std::max<long long>(1, std::min<long long>(sk.NW, T / kSkMinIt));
-    sk.T = (int)T;
-    a.C = out;
-    a.bias = bias;
-    const dim3 grid(sk.tdp > 0 ? kSkNW : sk.NW), block(256);
-    const dim3 rgrid(pl.bm * kSkBN / 1024, (unsigned)(tiles - sk.tdp));
-    const bool reduce = T > 0;
-    if (X6L && (pl.bm == 128 || small_f16)) {
-      // the x6 kernel stages its weights from the bf16 planes that pack() split once, behind
-      // the fp32 part of the same buffer (M > 64 <=> 128-row tiles; f16x3: every M)
-      const long long f32 = (long long)pl.ksteps * kCB * a.lda;
-      a.Ax6 = reinterpret_cast<const __bf16*>(packed + f32);
-      if constexpr (F16) {
-        // f16x3 / fp16: the image's absmax partials, then the GEMM with the pack's {sA, 1/sA}
-        if (img_part) {  // the caller's partials of this image (msl_absmax_partials, a BN kernel)
-          a.bpart = img_part;
-          a.bnpart = img_npart;
-        } else {
-          float* part = ws_partials(ws, ws_bytes, 1);
-          MSL_LAUNCH(k_absmax, dim3(kNPart), block, 0, st, img, (long long)cimg * P, 0LL, 1, part);
-          MSL_CHECK_LAUNCH();
-          a.bpart = part;
-          a.bnpart = kNPart;
-        }
-        a.ascale = packed + pack_tail_offset(f32) + kNPart;
-        // the image operand pre-split once for the whole GEMM (BP form, behind the pieces): pays on
-        // the layer4 3x3 GEMMs (M = 512: the split pass is shared by 4 row blocks and 9 taps), fwd
-        // 162 vs 174 us, dgrad 172 vs 185; loses where the pass is a large share (pointwise 39 vs
-        // 31 us, layer2 34 vs 31, ASPP 144 vs 135) - profiles/r03_bp_ab.txt
-        const bool bp = bp_form(taps, M, small_f16, MT == kMathH1P);
-        if (bp) {
-          f16x8* planes = reinterpret_cast<f16x8*>((char*)ws + fwd_piece_bytes(pl));
-          const long long n = (long long)a.ncb * 2 * P;
-          const dim3 sgrid((unsigned)std::min<long long>(cdiv(n, 256), 8192));
-          if constexpr (MT == kMathH1P)
-            MSL_LAUNCH(k_split_img<1>, sgrid, block, 0, st, img, cimg, a.ncb, P, a.bpart, a.bnpart, planes);
-          else
-            MSL_LAUNCH(k_split_img<2>, sgrid, block, 0, st, img, cimg, a.ncb, P, a.bpart, a.bnpart, planes);
-          MSL_CHECK_LAUNCH();
-          a.Bx6 = planes;
-        }
-        // pointwise: B rows are unshifted, so they move as dwordx4 (4 pixels per lane: 2 DMAs per
-        // wave and K-step instead of 8 dword ones): 1-4 us per call on the wide 1x1 GEMMs
-        // (profiles/r02_f16x3_pw_dma.txt)
-        // waves 1 x 4 (each 128 rows x 32 pixels): every wave splits only its own B columns
-        // (2 x 2 waves split each column twice); step 40.5 vs 40.9 ms on one box
-        // (profiles/r02_f16x3_waves.txt)
-        if (small_f16) {
-          MSL_TRY(launch_sk<64, 1, 4, 1, 4, MT>(accum, grid, block, st, a, sk, bp));
-        } else if (taps == 1 && dil0 == 0 && MT == kMathH3P && pl.bmx > 0) {
-          // wide tiles (r06): the plan, the grid and the reduce of that tile size
-          if constexpr (MT == kMathH3P) {
-            const int tm = cdiv(M, pl.bmx);
-            const SkArgs s2 = plan_sk(tm, pl.tiles_n, pl.kps, kSkNW, forms_of(forms).sk_hybrid, (float*)ws);
-            const dim3 g2(s2.tdp > 0 ? kSkNW : s2.NW);
-            const dim3 r2(pl.bmx * kSkBN / 1024, (unsigned)((long long)tm * pl.tiles_n - s2.tdp));
-            MSL_TRY(launch_sk<256, 1, 3, 1, 4, MT, true>(accum, g2, block, st, a, s2));
-            MSL_CHECK_LAUNCH();
-            if (s2.T > 0) MSL_LAUNCH((k_sk_reduce<256, kSkBN>), r2, block, 0, st, a, s2);
-            MSL_CHECK_LAUNCH();
-            return MSL_OK;
-          }
-        } else if (taps == 1 && dil0 == 0) {
-          if constexpr (MT == kMathH1P) {
-            if (pw2)
-              MSL_TRY(launch_sk<128, 2, 3, 1, 4, MT, true>(accum, grid, block, st, a, sk, bp));
-            else
-              MSL_TRY(launch_sk<128, 1, 4, 1, 4, MT, true>(accum, grid, block, st, a, sk, bp));
-          } else {
-            MSL_TRY(launch_sk<128, 1, 4, 1, 4, MT, true>(accum, grid, block, st, a, sk, bp));
-          }
-        } else if (bp && !accum && bq_form(taps, M, small_f16)) {
-          MSL_TRY(launch_sk<128, 1, 4, 2, 2, MT>(accum, grid, block, st, a, sk, bp));
-        } else {
-          MSL_TRY(launch_sk<128, 1, 4, 1, 4, MT>(accum, grid, block, st, a, sk, bp));
-        }
-      } else {
-        MSL_TRY(launch_sk<128, 1, 4, 2, 2, kMathX6P>(accum, grid, block, st, a, sk));
-      }
-      MSL_CHECK_LAUNCH();
-      if (reduce) {
-        if (small_f16)
-          MSL_LAUNCH((k_sk_reduce<64, kSkBN>), rgrid, block, 0, st, a, sk);
-        else
-          MSL_LAUNCH((k_sk_reduce<128, kSkBN>), rgrid, block, 0, st, a, sk);
-      }
-    } else if (pl.bm == 128) {
-      if (pl.G == 2)
-        MSL_TRY(launch_sk<128, 2, 2, 2, 2, MB>(accum, grid, block, st, a, sk));
-      else
-        MSL_TRY(launch_sk<128, 1, 3, 2, 2, MB>(accum, grid, block, st, a, sk));
-      MSL_CHECK_LAUNCH();
-      if (reduce) MSL_LAUNCH((k_sk_reduce<128, kSkBN>), rgrid, block, 0, st, a, sk);
-    } else if (pl.bm == 64) {
-      if (pl.G == 2)
-        MSL_TRY(launch_sk<64, 2, 2, 2, 2, MS>(accum, grid, block, st, a, sk));
-      else
-        MSL_TRY(launch_sk<64, 1, 3, 2, 2, MS>(accum, grid, block, st, a, sk));
-      MSL_CHECK_LAUNCH();
-      if (reduce) MSL_LAUNCH((k_sk_reduce<64, kSkBN>), rgrid, block, 0, st, a, sk);
-    } else {
-      MSL_TRY(launch_sk<32, 2, 2, 1, 4, MS>(accum, grid, block, st, a, sk));
-      MSL_CHECK_LAUNCH();
-      if (reduce) MSL_LAUNCH((k_sk_reduce<32, kSkBN>), rgrid, block, 0, st, a, sk);
-    }
-    MSL_CHECK_LAUNCH();
-    return MSL_OK;
-  }
-  // the split-K tile kernel (odd K-step count, M <= 32) has no bf16 form; x6 runs it in exact f32
-  if (MT == kMathBf16 || accum) return MSL_ERR_SHAPE;
-  dim3 grid(pl.tiles_n, pl.tiles_m, pl.S);
-  MSL_LAUNCH((k_igemm_fwd<64, 128, 16, 2, 2>), grid, dim3(256), 0, st, a);
-  MSL_CHECK_LAUNCH();
-  if (pl.S > 1) {
-    const long long n = (long long)M * P;
-    const int blocks = (int)std::min<long long>(cdiv(n, 256), 4096);
-    MSL_LAUNCH(k_reduce_slabs, dim3(blocks), dim3(256), 0, st, (const float*)ws, pl.S, n,
-                       out, 0, bias, nbias, M, P);
-    MSL_CHECK_LAUNCH();
-  }
-  return MSL_OK;
-}
-
-static bool bad_dims(int nbranch, int cin, int cout, int h, int w, int nimg = 1) {
-  return nbranch < 1 || nbranch > 2 || cin < 1 || cout < 1 || h < 1 || w < 1 || nimg < 1 ||
-         (long long)nimg * h * w > (1LL << 30);
-}
 
 // ---------------------------------------------------------------- shared by 3x3 and pointwise
 // A packed operand is the fp32 K-major pack [ksteps*16][lda] followed by its bf16x6 planes
@@ -854,158 +857,219 @@ static size_t wgrad_ws_bytes(int nbranch, int taps, int cin, int cout, int P, in
 }
 
 template <int MT>
-static int launch_wgrad(const float* x, const float* dy, float* dw, float* dbias, int nbranch,
-                        int taps, int cin, int cout, int h, int w, int nimg, int dil0, int dil1,
-                        int accumulate, void* ws, size_t ws_bytes, hipStream_t st,
-                        const float* x_part = nullptr, int x_npart = 0, const float* dy_part = nullptr,
-                        int dy_npart = 0) {
-  const int P = nimg * h * w;
+static int launch_wgrad(WgradCall c, void* ws, size_t ws_bytes, hipStream_t st) {
+  const ConvGeom& g = c.g;
+  const int P = g.nimg * g.h * g.w, taps = g.taps, nbranch = g.nbranch;
   constexpr bool F16 = MT == kMathH3P || MT == kMathH1P;
   constexpr bool X6L = MT == kMathX6 || F16;
   constexpr int MS = X6L ? kMathF32 : MT;  // the split forms only on 128x128 tiles (plan_wgrad)
   constexpr int MB = F16 ? kMathX6 : MT;   // k_wgrad_sk has no f16 form: x6 there
-  if (ws_bytes < wgrad_ws_bytes(nbranch, taps, cin, cout, P, w)) return MSL_ERR_WORKSPACE;
-  WgradPlan pl = plan_wgrad(nbranch, taps, cin, cout, P, X6L, w);
+  constexpr int MX = F16 ? MT : kMathX6;   // k_wgrad_x6's
+  if (ws_bytes < wgrad_ws_bytes(nbranch, taps, c.cin, c.cout, P, g.w)) return MSL_ERR_WORKSPACE;
+  WgradPlan pl = plan_wgrad(nbranch, taps, c.cin, c.cout, P, X6L, g.w);
   bool trans = false;
-  if (X6L && wgrad_swaps(nbranch, taps, cin, cout) && !dbias) {
-    WgradPlan ps = plan_wgrad(nbranch, taps, cout, cin, P, true, w);
+  if (X6L && wgrad_swaps(nbranch, taps, c.cin, c.cout) && !c.dbias) {
+    WgradPlan ps = plan_wgrad(nbranch, taps, c.cout, c.cin, P, true, g.w);
     if (ps.rx6) {  // dW^T = image . dY^T: M = cin (pre-split), N = cout
       pl = ps;
       trans = true;
-      std::swap(x, dy);
-      std::swap(x_part, dy_part);
-      std::swap(x_npart, dy_npart);
-      std::swap(cin, cout);
+      std::swap(c.x, c.dy);
+      std::swap(c.x_part, c.dy_part);
+      std::swap(c.x_npart, c.dy_npart);
+      std::swap(c.cin, c.cout);
     }
   }
+  const int cin = c.cin, cout = c.cout;
   if (pl.T * pl.nw >= (1LL << 31) || (long long)pl.nw * pl.slots * pl.bm * pl.bn * 4 >= (1LL << 31) || (long long)std::max(cin, cout) * P >= (1LL << 29) ||
       (long long)P + kWskBK >= (1LL << 22))
     return MSL_ERR_SHAPE;  // 32-bit index arithmetic, float pixel-row division in the kernel
   WskArgs a{};
-  a.dy = dy;
-  a.x = x;
-  a.dw = dw;
+  a.dy = c.dy;
+  a.x = c.x;
+  a.dw = c.dw;
   a.part = (float*)ws;
   a.M = cout;
   a.N = cin;
-  a.H = h;
-  a.W = w;
+  a.H = g.h;
+  a.W = g.w;
   a.P = P;
-  a.dil0 = dil0;
-  a.dil1 = dil1;
+  a.dil0 = g.dil0;
+  a.dil1 = g.dil1;
   a.taps = taps;
-  a.accumulate = accumulate;
+  a.accumulate = c.accumulate;
   a.slots = pl.slots;
-  a.invW = 1.0f / (float)w;
-  a.invH = 1.0f / (float)h;
+  a.invW = 1.0f / (float)g.w;
+  a.invH = 1.0f / (float)g.h;
   a.tiles_m = pl.tiles_m;
   a.tiles_n = pl.tiles_n;
   a.KS = pl.KS;
   a.NW = pl.nw;
   a.T = (int)pl.T;
   a.cbranch = (long long)cout * cin * taps;
-  a.dyx6 = nullptr;
   a.lda = pl.lda;
   a.nchunk = pl.nchunk;
   a.kchunk = pl.kchunk;
   a.ntiles = pl.tiles_m * pl.tiles_n * pl.ntap;
   a.trans = trans ? 1 : 0;
-  a.apart = nullptr;
-  a.bpart = nullptr;
-  a.anpart = a.bnpart = 0;
   const dim3 grid(pl.nw), block(256);
   const dim3 rgrid(cdiv((long long)pl.bm * pl.bn / 4 * taps, 256), pl.tiles_m * pl.tiles_n * nbranch), rblock(256);
+  // the GEMM
   if (pl.rx6) {
     bf16x8* planes = reinterpret_cast<bf16x8*>((char*)ws + wgrad_piece_bytes(pl));
     a.dyx6 = planes;
-    if constexpr (F16) {  // both operands' per-row absmax partials, then the per-row scaled split
-      const float* ap = dy_part;
-      const float* bp = x_part;
-      int an = dy_npart, bn = x_npart;
+    if constexpr (F16) {  // both operands' per-row absmax partials for the per-row scaled split
       // the caller's partials are one maximum per row (msl_absmax_partials, the BN kernels' per-
       // channel outputs); none given: reduce them here (after a swap the operands traded places)
-      float* rp = reinterpret_cast<float*>((char*)ws + wgrad_core_bytes(nbranch, taps, cin, cout, P, w));
-      if (!ap) {
-        const int e = absmax_rows(dy, cout, P, rp, st);
-        if (e != MSL_OK) return e;
-        ap = rp;
-        an = cout;
+      float* rp = reinterpret_cast<float*>((char*)ws + wgrad_core_bytes(nbranch, taps, cin, cout, P, g.w));
+      a.apart = c.dy_part;
+      a.anpart = c.dy_npart;
+      if (!a.apart) {
+        MSL_TRY(absmax_rows(c.dy, cout, P, rp, st));
+        a.apart = rp;
+        a.anpart = cout;
       }
-      if (!bp) {
+      a.bpart = c.x_part;
+      a.bnpart = c.x_npart;
+      if (!a.bpart) {
         float* r2 = rp + align_up((size_t)cout, 4);
-        const int e = absmax_rows(x, cin, P, r2, st);
-        if (e != MSL_OK) return e;
-        bp = r2;
-        bn = cin;
+        MSL_TRY(absmax_rows(c.x, cin, P, r2, st));
+        a.bpart = r2;
+        a.bnpart = cin;
       }
-      a.apart = ap;
-      a.bpart = bp;
-      a.anpart = an;
-      a.bnpart = bn;
-      a.rowscale = (an == cout && bn == cin) ? 1 : 0;
-      MSL_LAUNCH(k_split_rows<MT>, dim3(pl.lda / kSplitRowsR, cdiv(pl.KS, 16)), dim3(256), 0, st, dy, cout, P,
-                         pl.KS, pl.lda, planes, ap, an, a.rowscale);
-      MSL_CHECK_LAUNCH();
-      MSL_LAUNCH((k_wgrad_x6<MT>), grid, block, 0, st, a);
-    } else {
-      MSL_LAUNCH(k_split_rows<kMathX6>, dim3(pl.lda / kSplitRowsR, cdiv(pl.KS, 16)), dim3(256), 0, st, dy, cout, P,
-                         pl.KS, pl.lda, planes, (const float*)nullptr, 0);
-      MSL_CHECK_LAUNCH();
-      MSL_LAUNCH(k_wgrad_x6<kMathX6>, grid, block, 0, st, a);
+      a.rowscale = (a.anpart == cout && a.bnpart == cin) ? 1 : 0;
     }
+    MSL_LAUNCH(k_split_rows<MX>, dim3(pl.lda / kSplitRowsR, cdiv(pl.KS, 16)), block, 0, st, c.dy, cout, P, pl.KS,
+               pl.lda, planes, a.apart, a.anpart, a.rowscale);
     MSL_CHECK_LAUNCH();
-    // r06: S waves per 64 outputs, each summing every S-th piece (k_wsk_reduce_split), where a tile has >= 16 pieces
-    // (the 16- and 9-tile layer3 1x1 / layer2 3x3 gradients: 32-56 chunks; at 8 pieces, 512 -> 2048, it lost 4 us)
-    const long long tile_pieces = pl.nchunk > 0 ? pl.nchunk : cdiv((long long)pl.nw, (long long)a.ntiles);
-    if (kWskSplit > 1 && tile_pieces >= kWskSplitMinPieces)
-      MSL_LAUNCH((k_wsk_reduce_split<128, 128, kWskSplit>), dim3(cdiv(128LL * 128 / 4 * taps, 64), rgrid.y),
-                 dim3(64 * kWskSplit), 0, st, a);
-    else
-      MSL_LAUNCH((k_wsk_reduce<128, 128>), rgrid, rblock, 0, st, a);
+    MSL_LAUNCH(k_wgrad_x6<MX>, grid, block, 0, st, a);
   } else if (pl.bm == 128) {
     MSL_LAUNCH((k_wgrad_sk<128, 128, 2, 2, 2, MB>), grid, block, 0, st, a);
-    MSL_CHECK_LAUNCH();
-    MSL_LAUNCH((k_wsk_reduce<128, 128>), rgrid, rblock, 0, st, a);
   } else if (pl.bm == 64) {
     MSL_LAUNCH((k_wgrad_sk<64, 64, 2, 2, 2, MS>), grid, block, 0, st, a);
-    MSL_CHECK_LAUNCH();
-    // few tiles with many pieces each (the 33k-px 1x1 gradients: 4 tiles x ~128 pieces): 8 threads
-    // per output float4 (k_wsk_reduce_wide) instead of one serial chain of every piece
-    const long long pieces = cdiv((long long)pl.nw, std::max(1LL, pl.T / pl.KS));  // per (tile, tap)
-    if ((long long)rgrid.x * rgrid.y < 256 && pieces >= 16)
-      MSL_LAUNCH((k_wsk_reduce_wide<64, 64, 8>), dim3(cdiv((long long)64 * 64 / 4 * taps, 32), rgrid.y), rblock,
-                         0, st, a);
-    else
-      MSL_LAUNCH((k_wsk_reduce<64, 64>), rgrid, rblock, 0, st, a);
   } else {
     MSL_LAUNCH((k_wgrad_sk<32, 128, 2, 1, 4, MS>), grid, block, 0, st, a);
-    MSL_CHECK_LAUNCH();
-    MSL_LAUNCH((k_wsk_reduce<32, 128>), rgrid, rblock, 0, st, a);
   }
   MSL_CHECK_LAUNCH();
-  if (dbias) {
-    MSL_LAUNCH(k_bias_grad, dim3(cout), dim3(256), 0, st, dy, P, dbias, cout, nbranch,
-                       accumulate);
+  // the piece reduce
+  // r06, k_wgrad_x6: S waves per 64 outputs, each summing every S-th piece (k_wsk_reduce_split), where a tile has >= 16
+  // pieces (the 16- and 9-tile layer3 1x1 / layer2 3x3 gradients: 32-56 chunks; at 8 pieces, 512 -> 2048, it lost 4 us)
+  const long long x6_pieces = pl.nchunk > 0 ? pl.nchunk : cdiv((long long)pl.nw, (long long)a.ntiles);
+  // 64 x 64, few tiles with many pieces each (the 33k-px 1x1 gradients: 4 tiles x ~128 pieces): 8 threads per
+  // output float4 (k_wsk_reduce_wide) instead of one serial chain of every piece
+  const long long sk_pieces = cdiv((long long)pl.nw, std::max(1LL, pl.T / pl.KS));  // per (tile, tap)
+  if (pl.rx6 && kWskSplit > 1 && x6_pieces >= kWskSplitMinPieces)
+    MSL_LAUNCH((k_wsk_reduce_split<128, 128, kWskSplit>), dim3(cdiv(128LL * 128 / 4 * taps, 64), rgrid.y),
+               dim3(64 * kWskSplit), 0, st, a);
+  else if (pl.bm == 128)
+    MSL_LAUNCH((k_wsk_reduce<128, 128>), rgrid, rblock, 0, st, a);
+  else if (pl.bm == 64 && (long long)rgrid.x * rgrid.y < 256 && sk_pieces >= 16)
+    MSL_LAUNCH((k_wsk_reduce_wide<64, 64, 8>), dim3(cdiv((long long)64 * 64 / 4 * taps, 32), rgrid.y), rblock, 0, st, a);
+  else if (pl.bm == 64)
+    MSL_LAUNCH((k_wsk_reduce<64, 64>), rgrid, rblock, 0, st, a);
+  else
+    MSL_LAUNCH((k_wsk_reduce<32, 128>), rgrid, rblock, 0, st, a);
+  MSL_CHECK_LAUNCH();
+  if (c.dbias) {
+    MSL_LAUNCH(k_bias_grad, dim3(cout), block, 0, st, c.dy, P, c.dbias, cout, nbranch, c.accumulate);
     MSL_CHECK_LAUNCH();
   }
   return MSL_OK;
 }
 
-// the fp32 entry points: the kernel template of the call's f32 form
-template <typename... Args>
-static int fwd_f32(const msl_forms* forms, Args... args) {
-  if (forms_bad(forms)) return MSL_ERR_ARG;
+// ---------------------------------------------------------------- the entry points' families
+// Every conv entry point builds its call record and ends here.  fp32: the kernels of the call's f32_form,
+// any valid forms; bf16: bf16 MFMA; fp16: BASELINE config 5's fp16 MFMA path on the f16x3 machinery - each
+// operand tensor scaled by its power of two and rounded to fp16 once (the weights at pack time: the f16x3
+// packs' hi planes, so the forms must name the f16x3 fp32 form, the default), one v_mfma_f32_32x32x16_f16
+// per 16-deep slice, fp32 sums, the result unscaled exactly; its 64- / 32-row weight-gradient tiles run
+// exact f32 MFMA.
+enum Family { kFamF32, kFamBf16, kFamF16 };
+
+// the family's math (plan_fwd), or -1 for forms it cannot run (MSL_ERR_ARG)
+static int family_math(Family fam, const msl_forms* forms) {
+  if (forms_bad(forms)) return -1;
   const int form = forms_of(forms).f32_form;
-  if (form == kMathH3P) return launch_fwd_form<kMathH3P>(args...);
-  return form == kMathX6 ? launch_fwd_form<kMathX6>(args...) : launch_fwd_form<kMathF32>(args...);
+  if (fam == kFamF16) return form == kMathH3P ? kMathH1P : -1;
+  return fam == kFamBf16 ? kMathBf16 : form;
 }
 
-template <typename... Args>
-static int wgrad_f32(const msl_forms* forms, Args... args) {
-  if (forms_bad(forms)) return MSL_ERR_ARG;
-  const int form = forms_of(forms).f32_form;
-  if (form == kMathH3P) return launch_wgrad<kMathH3P>(args...);
-  return form == kMathX6 ? launch_wgrad<kMathX6>(args...) : launch_wgrad<kMathF32>(args...);
+static int run_fwd(Family fam, const FwdCall& c, const msl_forms* forms, void* ws, size_t ws_bytes,
+                   msl_stream_t stream) {
+  const int math = family_math(fam, forms);
+  if (math < 0 || bad_fwd(c)) return MSL_ERR_ARG;
+  return launch_fwd_form(math, c, forms, ws, ws_bytes, as_stream(stream));
+}
+
+static int run_wgrad(Family fam, const WgradCall& c, const msl_forms* forms, void* ws, size_t ws_bytes,
+                     msl_stream_t stream) {
+  const int math = family_math(fam, forms);
+  if (math < 0 || bad_wgrad(c)) return MSL_ERR_ARG;
+  hipStream_t st = as_stream(stream);
+  switch (math) {
+    case kMathH1P: return launch_wgrad<kMathH1P>(c, ws, ws_bytes, st);
+    case kMathBf16: return launch_wgrad<kMathBf16>(c, ws, ws_bytes, st);
+    case kMathH3P: return launch_wgrad<kMathH3P>(c, ws, ws_bytes, st);
+    case kMathX6: return launch_wgrad<kMathX6>(c, ws, ws_bytes, st);
+    default: return launch_wgrad<kMathF32>(c, ws, ws_bytes, st);
+  }
+}
+
+// The three operations behind the entry points, each in every family and geometry
+static int conv_fwd(Family fam, const ConvGeom& g, const float* x, const float* packed, const float* bias, float* y,
+                    int cin, int cout, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream,
+                    const float* x_part, int x_npart) {
+  FwdCall c{};
+  c.g = g;
+  c.img = x;
+  c.cimg = cin;
+  c.packed = packed;
+  c.bias = bias;
+  c.out = y;
+  c.M = cout;
+  c.img_part = x_part;
+  c.img_npart = x_npart;
+  c.res_nimg = 1;
+  return run_fwd(fam, c, forms, ws, ws_bytes, stream);
+}
+
+// res = null: dx (=|+=) W^T dy; else dx = mask(res) + W^T dy
+static int conv_dgrad(Family fam, const ConvGeom& g, const float* dy, const float* packed_dgrad, float* dx, int cin,
+                      int cout, int accumulate, const float* res, const unsigned long long* res_mask, int res_nimg,
+                      const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream, const float* dy_part,
+                      int dy_npart) {
+  FwdCall c{};
+  c.g = g;
+  c.img = dy;
+  c.cimg = cout;
+  c.packed = packed_dgrad;
+  c.out = dx;
+  c.M = cin;
+  c.accum = accumulate ? 1 : 0;
+  c.img_part = dy_part;
+  c.img_npart = dy_npart;
+  c.res = res;
+  c.res_mask = res_mask;
+  c.res_nimg = res_nimg;
+  return run_fwd(fam, c, forms, ws, ws_bytes, stream);
+}
+
+static int conv_wgrad(Family fam, const ConvGeom& g, const float* x, const float* dy, float* dw, float* dbias, int cin,
+                      int cout, int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream,
+                      const float* x_part, int x_npart, const float* dy_part, int dy_npart) {
+  WgradCall c{};
+  c.g = g;
+  c.x = x;
+  c.dy = dy;
+  c.dw = dw;
+  c.dbias = dbias;
+  c.cin = cin;
+  c.cout = cout;
+  c.accumulate = accumulate;
+  c.x_part = x_part;
+  c.x_npart = x_npart;
+  c.dy_part = dy_part;
+  c.dy_npart = dy_npart;
+  return run_wgrad(fam, c, forms, ws, ws_bytes, stream);
 }
 
 }  // namespace msl
@@ -1042,7 +1106,7 @@ const char* msl_status_string(int status) {
   }
 }
 
-// ------------------------------------------------------------------ dilated 3x3
+// ------------------------------------------------------------------ packs, workspaces, queries
 long long msl_dconv_packed_elems(int nbranch, int cin, int cout, int for_dgrad) {
   return packed_elems(nbranch, 9, cin, cout, for_dgrad);
 }
@@ -1090,58 +1154,7 @@ int msl_conv_pack_many(const msl_pack_job* jobs, const long long* block_start, i
   return MSL_OK;
 }
 
-size_t msl_dconv_fwd_workspace(int nbranch, int cin, int cout, int h, int w, int nimg) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg)) return 0;
-  const int P = nimg * h * w;
-  // large enough with or without a bias (the plan depends on it)
-  return std::max(fwd_ws_bytes(plan_fwd(nbranch, 9, cin, cout, P, false), cout, P, cin, 9),
-                  fwd_ws_bytes(plan_fwd(nbranch, 9, cin, cout, P, true), cout, P, cin, 9));
-}
-
-int msl_dconv_fwd(const float* x, const float* packed, const float* bias, float* y, int nbranch,
-                  int cin, int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
-                  size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !packed || !y || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return fwd_f32(forms, x, cin, packed, cout, bias, nbranch, y, nbranch, 9, h, w, nimg, dil0, dil1,
-                         forms, ws, ws_bytes, as_stream(stream));
-}
-
-size_t msl_dconv_dgrad_workspace(int nbranch, int cin, int cout, int h, int w, int nimg) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg)) return 0;
-  const int P = nimg * h * w;
-  return fwd_ws_bytes(plan_fwd(nbranch, 9, cout, cin, P, false), cin, P, cout, 9);
-}
-
-int msl_dconv_dgrad(const float* dy, const float* packed_dgrad, float* dx, int nbranch, int cin,
-                    int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
-                    size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !dy || !packed_dgrad || !dx || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return fwd_f32(forms, dy, cout, packed_dgrad, cin, nullptr, 0, dx, nbranch, 9, h, w, nimg, dil0, dil1,
-                         forms, ws, ws_bytes, as_stream(stream));
-}
-
-size_t msl_dconv_wgrad_workspace(int nbranch, int cin, int cout, int h, int w, int nimg) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg)) return 0;
-  const int P = nimg * h * w;
-  return wgrad_ws_bytes(nbranch, 9, cin, cout, P, w);
-}
-
-int msl_dconv_wgrad(const float* x, const float* dy, float* dw, float* dbias, int nbranch, int cin,
-                    int cout, int h, int w, int nimg, int dil0, int dil1, int accumulate, const msl_forms* forms, void* ws,
-                    size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !dy || !dw || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return wgrad_f32(forms, x, dy, dw, dbias, nbranch, 9, cin, cout, h, w, nimg, dil0, dil1, accumulate, ws,
-                      ws_bytes, as_stream(stream));
-}
-
-// ------------------------------------------------------------------ pointwise (1x1, stride 1)
-// A pointwise conv is the same GEMM with one unshifted tap (dilation 0) over the flat pixel axis.
+// A pointwise conv is the 3x3 GEMM with one unshifted tap (dilation 0) over the flat pixel axis.
 long long msl_pconv_packed_elems(int cin, int cout, int for_dgrad) {
   return packed_elems(1, 1, cin, cout, for_dgrad);
 }
@@ -1152,41 +1165,35 @@ int msl_pconv_pack(const float* w, int cin, int cout, int for_dgrad, float* pack
   return pack(w, 0, 1, 1, cin, cout, for_dgrad, packed, forms, as_stream(stream));
 }
 
-size_t msl_pconv_fwd_workspace(int cin, int cout, int p) {
-  if (bad_dims(1, cin, cout, 1, p)) return 0;
-  return fwd_ws_bytes(plan_fwd(1, 1, cin, cout, p, false), cout, p, cin, 1);
+size_t msl_dconv_fwd_workspace(int nbranch, int cin, int cout, int h, int w, int nimg) {
+  if (bad_dims(nbranch, cin, cout, h, w, nimg)) return 0;
+  return fwd_query_bytes(nbranch, 9, cin, cout, nimg * h * w);
 }
 
-int msl_pconv_fwd(const float* x, const float* packed, float* y, int cin, int cout, int p,
-                  const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(1, cin, cout, 1, p) || !x || !packed || !y) return MSL_ERR_ARG;
-  return fwd_f32(forms, x, cin, packed, cout, nullptr, 0, y, 1, 1, 1, p, 1, 0, 0, forms, ws,
-                         ws_bytes, as_stream(stream));
+size_t msl_dconv_dgrad_workspace(int nbranch, int cin, int cout, int h, int w, int nimg) {
+  if (bad_dims(nbranch, cin, cout, h, w, nimg)) return 0;
+  return fwd_query_bytes(nbranch, 9, cout, cin, nimg * h * w);
+}
+
+size_t msl_dconv_wgrad_workspace(int nbranch, int cin, int cout, int h, int w, int nimg) {
+  if (bad_dims(nbranch, cin, cout, h, w, nimg)) return 0;
+  return wgrad_ws_bytes(nbranch, 9, cin, cout, nimg * h * w, w);
+}
+
+size_t msl_pconv_fwd_workspace(int cin, int cout, int p) {
+  if (bad_dims(1, cin, cout, 1, p)) return 0;
+  return fwd_query_bytes(1, 1, cin, cout, p);
 }
 
 size_t msl_pconv_dgrad_workspace(int cin, int cout, int p) {
   if (bad_dims(1, cin, cout, 1, p)) return 0;
-  return fwd_ws_bytes(plan_fwd(1, 1, cout, cin, p, false), cin, p, cout, 1);
+  return fwd_query_bytes(1, 1, cout, cin, p);
 }
 
-int msl_pconv_dgrad(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
-                    const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(1, cin, cout, 1, p) || !dy || !packed_dgrad || !dx) return MSL_ERR_ARG;
-  return fwd_f32(forms, dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms,
-                         ws, ws_bytes, as_stream(stream));
+size_t msl_pconv_wgrad_workspace(int cin, int cout, int p) {
+  if (bad_dims(1, cin, cout, 1, p)) return 0;
+  return wgrad_ws_bytes(1, 1, cin, cout, p, p);
 }
-
-int msl_pconv_dgrad_acc(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
-                        int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(1, cin, cout, 1, p) || !dy || !packed_dgrad || !dx) return MSL_ERR_ARG;
-  if (!accumulate)
-    return fwd_f32(forms, dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms, ws, ws_bytes,
-                   as_stream(stream));
-  return fwd_f32(forms, dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms, ws, ws_bytes,
-                 as_stream(stream), 1);
-}
-
-static bool bad_parts(const float* p, int n) { return p && n < 1; }
 
 int msl_conv_wgrad_split(int nbranch, int taps, int cin, int cout, int h, int w, int nimg) {
   if (bad_dims(nbranch, cin, cout, h, w, nimg) || (taps != 1 && taps != 9)) return MSL_ERR_ARG;
@@ -1201,218 +1208,192 @@ int msl_absmax_partials(const float* x, int rows, int row_len, float* part, msl_
   return absmax_rows(x, rows, row_len, part, as_stream(stream));
 }
 
+// ------------------------------------------------------------------ fp32 math
+// The _sc entry points take the operands' absmax partials ((pointer, count), NULL = computed where the
+// form needs them); the plain ones are the same calls without partials.
 int msl_dconv_fwd_sc(const float* x, const float* packed, const float* bias, float* y, int nbranch,
                      int cin, int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
                      size_t ws_bytes, msl_stream_t stream, const float* x_part, int x_npart) {
-  if (bad_parts(x_part, x_npart)) return MSL_ERR_ARG;
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !packed || !y || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return fwd_f32(forms, x, cin, packed, cout, bias, nbranch, y, nbranch, 9, h, w, nimg, dil0, dil1, forms, ws, ws_bytes,
-                 as_stream(stream), 0, x_part, x_npart);
+  return conv_fwd(kFamF32, geom_3x3(nbranch, h, w, nimg, dil0, dil1), x, packed, bias, y, cin, cout, forms, ws,
+                  ws_bytes, stream, x_part, x_npart);
 }
 
 int msl_dconv_dgrad_sc(const float* dy, const float* packed_dgrad, float* dx, int nbranch, int cin,
                        int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
                        size_t ws_bytes, msl_stream_t stream, const float* dy_part, int dy_npart) {
-  if (bad_parts(dy_part, dy_npart)) return MSL_ERR_ARG;
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !dy || !packed_dgrad || !dx || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return fwd_f32(forms, dy, cout, packed_dgrad, cin, nullptr, 0, dx, nbranch, 9, h, w, nimg, dil0, dil1, forms, ws,
-                 ws_bytes, as_stream(stream), 0, dy_part, dy_npart);
+  return conv_dgrad(kFamF32, geom_3x3(nbranch, h, w, nimg, dil0, dil1), dy, packed_dgrad, dx, cin, cout, 0, nullptr,
+                    nullptr, 1, forms, ws, ws_bytes, stream, dy_part, dy_npart);
 }
 
 int msl_dconv_wgrad_sc(const float* x, const float* dy, float* dw, float* dbias, int nbranch, int cin,
                        int cout, int h, int w, int nimg, int dil0, int dil1, int accumulate, const msl_forms* forms, void* ws,
                        size_t ws_bytes, msl_stream_t stream, const float* x_part, int x_npart,
                        const float* dy_part, int dy_npart) {
-  if (bad_parts(x_part, x_npart) || bad_parts(dy_part, dy_npart)) return MSL_ERR_ARG;
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !dy || !dw || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return wgrad_f32(forms, x, dy, dw, dbias, nbranch, 9, cin, cout, h, w, nimg, dil0, dil1, accumulate, ws, ws_bytes,
-                   as_stream(stream), x_part, x_npart, dy_part, dy_npart);
+  return conv_wgrad(kFamF32, geom_3x3(nbranch, h, w, nimg, dil0, dil1), x, dy, dw, dbias, cin, cout, accumulate,
+                    forms, ws, ws_bytes, stream, x_part, x_npart, dy_part, dy_npart);
 }
 
 int msl_pconv_fwd_sc(const float* x, const float* packed, float* y, int cin, int cout, int p,
                      const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream, const float* x_part,
                      int x_npart) {
-  if (bad_parts(x_part, x_npart)) return MSL_ERR_ARG;
-  if (bad_dims(1, cin, cout, 1, p) || !x || !packed || !y) return MSL_ERR_ARG;
-  return fwd_f32(forms, x, cin, packed, cout, nullptr, 0, y, 1, 1, 1, p, 1, 0, 0, forms, ws, ws_bytes,
-                 as_stream(stream), 0, x_part, x_npart);
+  return conv_fwd(kFamF32, geom_1x1(p), x, packed, nullptr, y, cin, cout, forms, ws, ws_bytes, stream, x_part,
+                  x_npart);
 }
 
 int msl_pconv_dgrad_acc_sc(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
                            int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream,
                            const float* dy_part, int dy_npart) {
-  if (bad_parts(dy_part, dy_npart)) return MSL_ERR_ARG;
-  if (bad_dims(1, cin, cout, 1, p) || !dy || !packed_dgrad || !dx) return MSL_ERR_ARG;
-  return fwd_f32(forms, dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms, ws, ws_bytes,
-                 as_stream(stream), accumulate ? 1 : 0, dy_part, dy_npart);
+  return conv_dgrad(kFamF32, geom_1x1(p), dy, packed_dgrad, dx, cin, cout, accumulate, nullptr, nullptr, 1, forms,
+                    ws, ws_bytes, stream, dy_part, dy_npart);
 }
 
 int msl_pconv_dgrad_resmask_sc(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
                                const float* res, const unsigned long long* res_mask, int nimg, const msl_forms* forms,
                                void* ws, size_t ws_bytes, msl_stream_t stream, const float* dy_part, int dy_npart) {
-  if (bad_parts(dy_part, dy_npart)) return MSL_ERR_ARG;
-  if (bad_dims(1, cin, cout, 1, p) || !dy || !packed_dgrad || !dx || !res || !res_mask || nimg < 1 || p % nimg)
-    return MSL_ERR_ARG;
-  return fwd_f32(forms, dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms, ws, ws_bytes,
-                 as_stream(stream), 1, dy_part, dy_npart, res, res_mask, nimg);
+  if (!res) return MSL_ERR_ARG;
+  return conv_dgrad(kFamF32, geom_1x1(p), dy, packed_dgrad, dx, cin, cout, 1, res, res_mask, nimg, forms, ws,
+                    ws_bytes, stream, dy_part, dy_npart);
 }
 
 int msl_pconv_wgrad_sc(const float* x, const float* dy, float* dw, int cin, int cout, int p,
                        int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream, const float* x_part,
                        int x_npart, const float* dy_part, int dy_npart) {
-  if (bad_parts(x_part, x_npart) || bad_parts(dy_part, dy_npart)) return MSL_ERR_ARG;
-  if (bad_dims(1, cin, cout, 1, p) || !x || !dy || !dw) return MSL_ERR_ARG;
-  return wgrad_f32(forms, x, dy, dw, nullptr, 1, 1, cin, cout, 1, p, 1, 0, 0, accumulate, ws, ws_bytes, as_stream(stream),
-                   x_part, x_npart, dy_part, dy_npart);
+  return conv_wgrad(kFamF32, geom_1x1(p), x, dy, dw, nullptr, cin, cout, accumulate, forms, ws, ws_bytes, stream,
+                    x_part, x_npart, dy_part, dy_npart);
 }
 
-size_t msl_pconv_wgrad_workspace(int cin, int cout, int p) {
-  if (bad_dims(1, cin, cout, 1, p)) return 0;
-  return wgrad_ws_bytes(1, 1, cin, cout, p, p);
+int msl_dconv_fwd(const float* x, const float* packed, const float* bias, float* y, int nbranch,
+                  int cin, int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
+                  size_t ws_bytes, msl_stream_t stream) {
+  return msl_dconv_fwd_sc(x, packed, bias, y, nbranch, cin, cout, h, w, nimg, dil0, dil1, forms, ws, ws_bytes, stream,
+                          nullptr, 0);
+}
+
+int msl_dconv_dgrad(const float* dy, const float* packed_dgrad, float* dx, int nbranch, int cin,
+                    int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
+                    size_t ws_bytes, msl_stream_t stream) {
+  return msl_dconv_dgrad_sc(dy, packed_dgrad, dx, nbranch, cin, cout, h, w, nimg, dil0, dil1, forms, ws, ws_bytes,
+                            stream, nullptr, 0);
+}
+
+int msl_dconv_wgrad(const float* x, const float* dy, float* dw, float* dbias, int nbranch, int cin,
+                    int cout, int h, int w, int nimg, int dil0, int dil1, int accumulate, const msl_forms* forms, void* ws,
+                    size_t ws_bytes, msl_stream_t stream) {
+  return msl_dconv_wgrad_sc(x, dy, dw, dbias, nbranch, cin, cout, h, w, nimg, dil0, dil1, accumulate, forms, ws,
+                            ws_bytes, stream, nullptr, 0, nullptr, 0);
+}
+
+int msl_pconv_fwd(const float* x, const float* packed, float* y, int cin, int cout, int p,
+                  const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
+  return msl_pconv_fwd_sc(x, packed, y, cin, cout, p, forms, ws, ws_bytes, stream, nullptr, 0);
+}
+
+int msl_pconv_dgrad_acc(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
+                        int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
+  return msl_pconv_dgrad_acc_sc(dy, packed_dgrad, dx, cin, cout, p, accumulate, forms, ws, ws_bytes, stream, nullptr,
+                                0);
+}
+
+int msl_pconv_dgrad(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
+                    const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
+  return msl_pconv_dgrad_acc(dy, packed_dgrad, dx, cin, cout, p, 0, forms, ws, ws_bytes, stream);
 }
 
 int msl_pconv_wgrad(const float* x, const float* dy, float* dw, int cin, int cout, int p,
                     int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(1, cin, cout, 1, p) || !x || !dy || !dw) return MSL_ERR_ARG;
-  return wgrad_f32(forms, x, dy, dw, nullptr, 1, 1, cin, cout, 1, p, 1, 0, 0, accumulate, ws, ws_bytes,
-                      as_stream(stream));
+  return msl_pconv_wgrad_sc(x, dy, dw, cin, cout, p, accumulate, forms, ws, ws_bytes, stream, nullptr, 0, nullptr, 0);
 }
 
-
-// ------------------------------------------------------------------ BF16-MFMA forms
+// ------------------------------------------------------------------ bf16 math
 // Same operands, workspaces and results layout; products in bf16 (RNE from the fp32 operands),
-// sums in fp32 (BASELINE config 5's fp16/bf16 MFMA path).
+// sums in fp32 (BASELINE config 5's fp16/bf16 MFMA path).  No partials, no accumulate epilogue.
 int msl_dconv_fwd_bf16(const float* x, const float* packed, const float* bias, float* y, int nbranch,
                   int cin, int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
                   size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !packed || !y || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return launch_fwd_form<kMathBf16>(x, cin, packed, cout, bias, nbranch, y, nbranch, 9, h, w, nimg, dil0, dil1,
-                         forms, ws, ws_bytes, as_stream(stream));
+  return conv_fwd(kFamBf16, geom_3x3(nbranch, h, w, nimg, dil0, dil1), x, packed, bias, y, cin, cout, forms, ws,
+                  ws_bytes, stream, nullptr, 0);
 }
 
 int msl_dconv_dgrad_bf16(const float* dy, const float* packed_dgrad, float* dx, int nbranch, int cin,
                     int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws,
                     size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !dy || !packed_dgrad || !dx || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return launch_fwd_form<kMathBf16>(dy, cout, packed_dgrad, cin, nullptr, 0, dx, nbranch, 9, h, w, nimg, dil0, dil1,
-                         forms, ws, ws_bytes, as_stream(stream));
+  return conv_dgrad(kFamBf16, geom_3x3(nbranch, h, w, nimg, dil0, dil1), dy, packed_dgrad, dx, cin, cout, 0, nullptr,
+                    nullptr, 1, forms, ws, ws_bytes, stream, nullptr, 0);
 }
 
 int msl_dconv_wgrad_bf16(const float* x, const float* dy, float* dw, float* dbias, int nbranch, int cin,
                     int cout, int h, int w, int nimg, int dil0, int dil1, int accumulate, const msl_forms* forms, void* ws,
                     size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !dy || !dw || dil0 < 1 ||
-      (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  if (forms_bad(forms)) return MSL_ERR_ARG;
-  return launch_wgrad<kMathBf16>(x, dy, dw, dbias, nbranch, 9, cin, cout, h, w, nimg, dil0, dil1, accumulate, ws,
-                      ws_bytes, as_stream(stream));
+  return conv_wgrad(kFamBf16, geom_3x3(nbranch, h, w, nimg, dil0, dil1), x, dy, dw, dbias, cin, cout, accumulate,
+                    forms, ws, ws_bytes, stream, nullptr, 0, nullptr, 0);
 }
 
 int msl_pconv_fwd_bf16(const float* x, const float* packed, float* y, int cin, int cout, int p,
                   const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(1, cin, cout, 1, p) || !x || !packed || !y) return MSL_ERR_ARG;
-  return launch_fwd_form<kMathBf16>(x, cin, packed, cout, nullptr, 0, y, 1, 1, 1, p, 1, 0, 0, forms, ws,
-                         ws_bytes, as_stream(stream));
+  return conv_fwd(kFamBf16, geom_1x1(p), x, packed, nullptr, y, cin, cout, forms, ws, ws_bytes, stream, nullptr, 0);
 }
 
 int msl_pconv_dgrad_bf16(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
                     const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(1, cin, cout, 1, p) || !dy || !packed_dgrad || !dx) return MSL_ERR_ARG;
-  return launch_fwd_form<kMathBf16>(dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms,
-                         ws, ws_bytes, as_stream(stream));
+  return conv_dgrad(kFamBf16, geom_1x1(p), dy, packed_dgrad, dx, cin, cout, 0, nullptr, nullptr, 1, forms, ws,
+                    ws_bytes, stream, nullptr, 0);
 }
 
 int msl_pconv_wgrad_bf16(const float* x, const float* dy, float* dw, int cin, int cout, int p,
                     int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (bad_dims(1, cin, cout, 1, p) || !x || !dy || !dw || forms_bad(forms)) return MSL_ERR_ARG;
-  return launch_wgrad<kMathBf16>(x, dy, dw, nullptr, 1, 1, cin, cout, 1, p, 1, 0, 0, accumulate, ws, ws_bytes,
-                      as_stream(stream));
+  return conv_wgrad(kFamBf16, geom_1x1(p), x, dy, dw, nullptr, cin, cout, accumulate, forms, ws, ws_bytes, stream,
+                    nullptr, 0, nullptr, 0);
 }
 
-// ------------------------------------------------------------------ FP16-MFMA forms
-// BASELINE config 5's fp16 MFMA path on the f16x3 machinery: each operand tensor scaled by its
-// power of two and rounded to fp16 once (the weights at pack time: the f16x3 packs' hi planes,
-// so packs must be made in the f16x3 fp32 form, the default), one v_mfma_f32_32x32x16_f16 per
-// 16-deep slice, fp32 sums, the result unscaled exactly.  The 64- / 32-row tiles (M <= 64) run
-// exact f32 MFMA.  Partials as in the _sc entry points ((pointer, count), NULL = computed).
-static bool f16_ready(const msl_forms* forms) { return !forms_bad(forms) && forms_of(forms).f32_form == kMathH3P; }
-
+// ------------------------------------------------------------------ fp16 math
+// Partials as in the _sc entry points.
 int msl_dconv_fwd_f16(const float* x, const float* packed, const float* bias, float* y, int nbranch, int cin,
                       int cout, int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws, size_t ws_bytes,
                       msl_stream_t stream, const float* x_part, int x_npart) {
-  if (!f16_ready(forms) || bad_parts(x_part, x_npart) || bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !packed || !y ||
-      dil0 < 1 || (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return launch_fwd_form<kMathH1P>(x, cin, packed, cout, bias, nbranch, y, nbranch, 9, h, w, nimg, dil0, dil1, forms,
-                                   ws, ws_bytes, as_stream(stream), 0, x_part, x_npart);
+  return conv_fwd(kFamF16, geom_3x3(nbranch, h, w, nimg, dil0, dil1), x, packed, bias, y, cin, cout, forms, ws,
+                  ws_bytes, stream, x_part, x_npart);
 }
 
 int msl_dconv_dgrad_f16(const float* dy, const float* packed_dgrad, float* dx, int nbranch, int cin, int cout,
                         int h, int w, int nimg, int dil0, int dil1, const msl_forms* forms, void* ws, size_t ws_bytes,
                         msl_stream_t stream, const float* dy_part, int dy_npart) {
-  if (!f16_ready(forms) || bad_parts(dy_part, dy_npart) || bad_dims(nbranch, cin, cout, h, w, nimg) || !dy || !packed_dgrad ||
-      !dx || dil0 < 1 || (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return launch_fwd_form<kMathH1P>(dy, cout, packed_dgrad, cin, nullptr, 0, dx, nbranch, 9, h, w, nimg, dil0, dil1,
-                                   forms, ws, ws_bytes, as_stream(stream), 0, dy_part, dy_npart);
+  return conv_dgrad(kFamF16, geom_3x3(nbranch, h, w, nimg, dil0, dil1), dy, packed_dgrad, dx, cin, cout, 0, nullptr,
+                    nullptr, 1, forms, ws, ws_bytes, stream, dy_part, dy_npart);
 }
 
 int msl_dconv_wgrad_f16(const float* x, const float* dy, float* dw, float* dbias, int nbranch, int cin, int cout,
                         int h, int w, int nimg, int dil0, int dil1, int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes,
                         msl_stream_t stream, const float* x_part, int x_npart, const float* dy_part, int dy_npart) {
-  if (!f16_ready(forms) || bad_parts(x_part, x_npart) || bad_parts(dy_part, dy_npart) ||
-      bad_dims(nbranch, cin, cout, h, w, nimg) || !x || !dy || !dw || dil0 < 1 || (nbranch == 2 && dil1 < 1))
-    return MSL_ERR_ARG;
-  return launch_wgrad<kMathH1P>(x, dy, dw, dbias, nbranch, 9, cin, cout, h, w, nimg, dil0, dil1, accumulate, ws, ws_bytes,
-                                as_stream(stream), x_part, x_npart, dy_part, dy_npart);
+  return conv_wgrad(kFamF16, geom_3x3(nbranch, h, w, nimg, dil0, dil1), x, dy, dw, dbias, cin, cout, accumulate,
+                    forms, ws, ws_bytes, stream, x_part, x_npart, dy_part, dy_npart);
 }
 
 int msl_pconv_fwd_f16(const float* x, const float* packed, float* y, int cin, int cout, int p, const msl_forms* forms,
                       void* ws, size_t ws_bytes, msl_stream_t stream, const float* x_part, int x_npart) {
-  if (!f16_ready(forms) || bad_parts(x_part, x_npart) || bad_dims(1, cin, cout, 1, p) || !x || !packed || !y)
-    return MSL_ERR_ARG;
-  return launch_fwd_form<kMathH1P>(x, cin, packed, cout, nullptr, 0, y, 1, 1, 1, p, 1, 0, 0, forms, ws, ws_bytes,
-                                   as_stream(stream), 0, x_part, x_npart);
+  return conv_fwd(kFamF16, geom_1x1(p), x, packed, nullptr, y, cin, cout, forms, ws, ws_bytes, stream, x_part,
+                  x_npart);
 }
 
 int msl_pconv_dgrad_f16(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
                         int accumulate, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream,
                         const float* dy_part, int dy_npart) {
-  if (!f16_ready(forms) || bad_parts(dy_part, dy_npart) || bad_dims(1, cin, cout, 1, p) || !dy || !packed_dgrad || !dx)
-    return MSL_ERR_ARG;
-  return launch_fwd_form<kMathH1P>(dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms, ws,
-                                   ws_bytes, as_stream(stream), accumulate ? 1 : 0, dy_part, dy_npart);
+  return conv_dgrad(kFamF16, geom_1x1(p), dy, packed_dgrad, dx, cin, cout, accumulate, nullptr, nullptr, 1, forms,
+                    ws, ws_bytes, stream, dy_part, dy_npart);
 }
 
 int msl_pconv_dgrad_resmask_f16(const float* dy, const float* packed_dgrad, float* dx, int cin, int cout, int p,
                                 const float* res, const unsigned long long* res_mask, int nimg, const msl_forms* forms,
                                 void* ws, size_t ws_bytes, msl_stream_t stream, const float* dy_part, int dy_npart) {
-  if (!f16_ready(forms) || bad_parts(dy_part, dy_npart) || bad_dims(1, cin, cout, 1, p) || !dy || !packed_dgrad || !dx ||
-      !res || !res_mask || nimg < 1 || p % nimg)
-    return MSL_ERR_ARG;
-  return launch_fwd_form<kMathH1P>(dy, cout, packed_dgrad, cin, nullptr, 0, dx, 1, 1, 1, p, 1, 0, 0, forms, ws,
-                                   ws_bytes, as_stream(stream), 1, dy_part, dy_npart, res, res_mask, nimg);
+  if (!res) return MSL_ERR_ARG;
+  return conv_dgrad(kFamF16, geom_1x1(p), dy, packed_dgrad, dx, cin, cout, 1, res, res_mask, nimg, forms, ws,
+                    ws_bytes, stream, dy_part, dy_npart);
 }
 
 int msl_pconv_wgrad_f16(const float* x, const float* dy, float* dw, int cin, int cout, int p, int accumulate, const msl_forms* forms,
                         void* ws, size_t ws_bytes, msl_stream_t stream, const float* x_part, int x_npart,
                         const float* dy_part, int dy_npart) {
-  if (!f16_ready(forms) || bad_parts(x_part, x_npart) || bad_parts(dy_part, dy_npart) || bad_dims(1, cin, cout, 1, p) ||
-      !x || !dy || !dw)
-    return MSL_ERR_ARG;
-  return launch_wgrad<kMathH1P>(x, dy, dw, nullptr, 1, 1, cin, cout, 1, p, 1, 0, 0, accumulate, ws, ws_bytes,
-                                as_stream(stream), x_part, x_npart, dy_part, dy_npart);
+  return conv_wgrad(kFamF16, geom_1x1(p), x, dy, dw, nullptr, cin, cout, accumulate, forms, ws, ws_bytes, stream,
+                    x_part, x_npart, dy_part, dy_npart);
 }
 
 }  // extern "C"

@@ -946,7 +946,7 @@ __device__ __forceinline__ int sk_start(int w, int T, int NW) { return (int)((un
 // weights and a contiguous pixel range (r02 layer3 fwd: 66 vs 154 MB fetched per launch with m
 // fastest; profiles/r02_sk_tile_order.txt).  gm > 1: groups of gm m-blocks, m fastest inside a
 // group - the gm tiles of one pixel block run on neighbouring workers, so the image block is
-// fetched once (r04: the pointwise and layer4 GEMMs, dconv.hip launch_fwd_form).
+// fetched once (r04: the pointwise and layer4 GEMMs, dconv.hip plan_sk).
 __device__ __forceinline__ void sk_tile(int t, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
   if (gm <= 1) {
     tm = t / tiles_n;
@@ -1004,10 +1004,8 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
   constexpr int NQ = H3 ? 4 : 6;  // (plane, k half) blocks of one pre-split K-step in the pack
   constexpr int NQL = H1 ? 2 : NQ;  // of them staged (fp16 math: plane 0's two halves)
   static_assert(!APRE || BM % 64 == 0, "pre-split A: 64-row DMA pieces");
-  // BD: 1 x 4 waves (128 rows x 32 pixels each); the pre-split image (BP) also in 2 x 2 waves (64 x 64, r06)
-  static_assert(!BD || (H3 && G == 1 && STAGES == 4 &&
-                        ((WM == 1 && WN == 4 && TN == 1) || (BP && WM == 2 && WN == 2 && TM == 2 && TN == 2))),
-                "BD form");
+  // BD: 1 x 4 waves (128 or 64 rows x 32 pixels each)
+  static_assert(!BD || (H3 && G == 1 && STAGES == 4 && WM == 1 && WN == 4 && TN == 1), "BD form");
   constexpr int A_STAGE = APRE ? G * 4 * NQL * BM : BK * BM;
   constexpr int STAGE = A_STAGE + (BD ? 0 : BK * BN);
   constexpr int A_ROWS_PER_INST = 256 / BM;
@@ -1222,7 +1220,7 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
           }
         } else if constexpr (BD) {
           // channels cb16 + 8h + j of this lane's pixel.  The BD form runs only with every 16-channel
-          // block full (cimg % 16 == 0, launch_sk): the channel offset is wave-uniform, so it rides in
+          // block full (cimg % 16 == 0, plan_fwd): the channel offset is wave-uniform, so it rides in
           // the scalar soffset and the eight loads share one address VGPR (r04: a per-channel bound
           // check cost ~32 VALU per K-step, and a second load path made the compiler's wait counts
           // drain the queue); an out-of-image pixel's voffset >= 2^31 is out of range whatever the

@@ -985,7 +985,7 @@ static int loss_bwd(const float* L1, const float* L2, const int64_t* labels, con
   hipStream_t st = as_stream(s);
   float* T = (float*)ws;
   MSL_DISPATCH_C(c, CM, {
-    auto kern = k_bwd_rows<KIND, CM>;
+    constexpr auto kern = k_bwd_rows<KIND, CM>;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     MSL_LAUNCH(kern, dim3(ho, rows_chunks(g)), dim3(256), lds, st, L1, L2, labels, gin_hi, g, thr,
                        stats, gout, T, rows_wmax(g));

@@ -10,16 +10,20 @@
 
 // Every kernel launch of the library goes through MSL_LAUNCH (r06): the block's thread
 // count is checked against the kernel's own __launch_bounds__ (its code object's max flat workgroup size,
-// hipFuncGetAttributes, queried once per launch site) before the launch, and an oversized block returns
+// hipFuncGetAttributes, queried once per kernel) before the launch, and an oversized block returns
 // MSL_ERR_LAUNCH from the entry point instead of launching.  r05's kg2 experiment launched 256-thread
 // helper kernels with a 512-thread block: an asynchronous "unspecified launch failure", not a status.
-#define MSL_LAUNCH(K, GRID, BLOCK, SHM, ST, ...)                                                    \
+// The cached bound belongs to the kernel, not to the launch site: K is a constant expression (a site that
+// picks among kernels at run time writes one MSL_LAUNCH per kernel), or the kernel comes from a table
+// that holds its bound beside the pointer (MSL_LAUNCH_ENTRY).
+#define MSL_LAUNCH_ENTRY(K, BOUND, GRID, BLOCK, SHM, ST, ...)                                       \
   do {                                                                                              \
-    static std::atomic<int> msl_bound_{0};                                                          \
-    const int msl_e_ = ::msl::launch_guard(reinterpret_cast<const void*>(K), dim3(BLOCK), msl_bound_); \
+    const int msl_e_ = ::msl::launch_guard(reinterpret_cast<const void*>(K), dim3(BLOCK), BOUND);   \
     if (msl_e_ != MSL_OK) return msl_e_;                                                            \
     hipLaunchKernelGGL(K, GRID, BLOCK, SHM, ST, __VA_ARGS__);                                       \
   } while (0)
+#define MSL_LAUNCH(K, GRID, BLOCK, SHM, ST, ...) \
+  MSL_LAUNCH_ENTRY(K, ::msl::kernel_bound<K>(), GRID, BLOCK, SHM, ST, __VA_ARGS__)
 
 #define MSL_TRY(...)                 \
   do {                               \
@@ -47,6 +51,13 @@ static inline int launch_guard(const void* k, dim3 block, std::atomic<int>& boun
     bound.store(b, std::memory_order_relaxed);
   }
   return (long long)block.x * block.y * block.z > b ? MSL_ERR_LAUNCH : MSL_OK;
+}
+
+// kernel K's cached launch bound (0 = not queried yet)
+template <auto K>
+static inline std::atomic<int>& kernel_bound() {
+  static std::atomic<int> bound{0};
+  return bound;
 }
 
 static inline hipStream_t as_stream(msl_stream_t s) { return reinterpret_cast<hipStream_t>(s); }

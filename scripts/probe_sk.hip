@@ -2,7 +2,7 @@
 // stamps (fwd_sk_body PROF) - where a K-step of the loop spends its cycles.  Not part of the library:
 //   hipcc --offload-arch=gfx950 -O3 -fPIC -shared -std=c++17 scripts/probe_sk.hip maxsquareloss_amd/csrc/bn.hip \
 //         -o scripts/probe_sk.so
-// driven by scripts/probe_sk.py.  The launch restates launch_fwd_form's BD f16x3 path (dconv.hip).
+// driven by scripts/probe_sk.py.  The launch follows plan_fwd's BD f16x3 plan (dconv.hip), always with the image operand in registers.
 #include "../maxsquareloss_amd/csrc/dconv.hip"
 
 extern "C" int probe_bd_fwd(const float* x, const float* packed, float* y, int cin, int cout, int h, int w, int nimg,
@@ -10,11 +10,8 @@ extern "C" int probe_bd_fwd(const float* x, const float* packed, float* y, int c
                             unsigned long long* prof, int with_prof, msl_stream_t stream) {
   hipStream_t st = as_stream(stream);
   const int P = nimg * h * w;
-  FwdPlan pl = plan_fwd(1, 9, cin, cout, P, false);
-  if (!pl.sk || pl.bm != 128 || cin % kCB) return MSL_ERR_SHAPE;
-  pl.G = 1;
-  pl.bk = kCB;
-  pl.kps = pl.ksteps;
+  const FwdPlan pl = plan_fwd(kMathH3P, 1, 9, cin, cout, P, 0, dil, nullptr);
+  if (!pl.sk || pl.form.bm != 128 || pl.form.bform == kBLds) return MSL_ERR_SHAPE;
   FwdArgs a{};
   a.A = packed;
   a.B = x;
@@ -36,20 +33,11 @@ extern "C" int probe_bd_fwd(const float* x, const float* packed, float* y, int c
   a.bpart = x_part;
   a.bnpart = x_npart;
   a.ascale = packed + pack_tail_offset(f32) + kNPart;
-  SkArgs sk{};
+  if (ws_bytes < fwd_piece_bytes(9, cout)) return MSL_ERR_WORKSPACE;
+  SkArgs sk = pl.sched;
   sk.part = (float*)ws;
-  sk.tiles_m = pl.tiles_m;
-  sk.tiles_n = pl.tiles_n;
-  sk.KS = pl.kps;
-  const long long tiles = (long long)pl.tiles_m * pl.tiles_n;
+  const long long tiles = (long long)pl.tiles_m * pl.tiles_n, T = sk.T;
   const int nwk = kSkNW;
-  if (ws_bytes < (size_t)nwk * 2 * 128 * kSkBN * 4) return MSL_ERR_WORKSPACE;
-  sk.tdp = tiles >= nwk ? (int)(tiles / nwk * nwk) : 0;
-  sk.gm = sk.tdp > 0 ? pl.tiles_m : 1;
-  const long long T = (tiles - sk.tdp) * sk.KS;
-  sk.NW = (int)std::min<long long>(nwk, T);
-  if (sk.tdp > 0) sk.NW = (int)std::max<long long>(1, std::min<long long>(sk.NW, T / 8));
-  sk.T = (int)T;
   sk.prof = prof;
   const dim3 grid(sk.tdp > 0 ? nwk : sk.NW), block(256);
   // with_prof: 1 stamps; 2, 4, 8, 6, 14 timing-only ablations, 16 a BN-apply of the image operand
@@ -81,7 +69,6 @@ extern "C" int probe_bd_fwd(const float* x, const float* packed, float* y, int c
 
 extern "C" int probe_workers(int cin, int cout, int h, int w, int nimg) {
   const int P = nimg * h * w;
-  FwdPlan pl = plan_fwd(1, 9, cin, cout, P, false);
-  const long long tiles = (long long)pl.tiles_m * pl.tiles_n;
-  return tiles >= kSkNW ? kSkNW : (int)std::min<long long>(kSkNW, tiles * pl.ksteps);
+  const SkArgs sk = plan_fwd(kMathH3P, 1, 9, cin, cout, P, 0, 1, nullptr).sched;
+  return sk.tdp > 0 ? kSkNW : sk.NW;
 }
