@@ -331,6 +331,43 @@ int msl_pconv_wgrad_f16(const float* x, const float* dy, float* dw, int cin, int
 int msl_conv_wgrad_split(int nbranch, int taps, int cin, int cout, int h, int w, int nimg);
 
 /* ------------------------------------------------------------------------
+ * The plan of a forward-form call (forward and data gradient of every family), as a host-only
+ * query: no launch, no pointers, usable without a GPU.  The tests hold every reachable
+ * (kernel, schedule) to fp64 through it (tests/conv_form_cases.py).  Additive: ABI 3.
+ * Replaces nothing in the reference.
+ * ---------------------------------------------------------------------- */
+/* One instantiation of the stream-K kernel (its template arguments). */
+typedef struct msl_conv_form {
+  int bm, G, stages, wm, wn; /* tile rows, K-steps per LDS stage, stages, wave layout */
+  int pw;                    /* pointwise image rows (dwordx4 pieces) */
+  int math;                  /* 0 exact f32, 1 bf16, 2 bf16x6 split in the loop, 3 bf16x6 on pre-split
+                                weights, 5 f16x3, 8 fp16 */
+  int acc;                   /* the accumulate epilogue */
+  int bform;                 /* image operand: 0 through LDS, 1 straight to registers, 2 pre-split */
+} msl_conv_form;
+int msl_conv_fwd_form_count(void);                            /* instantiations built */
+int msl_conv_fwd_form_describe(int row, msl_conv_form* out); /* MSL_ERR_ARG outside [0, count) or NULL */
+typedef struct msl_conv_fwd_plan_info {
+  int row;      /* the instantiation the call launches (msl_conv_fwd_form_describe); -1: none (the split-K
+                   tile kernel, or a form that is not built) */
+  int stream_k; /* 1 stream-K, 0 the split-K tile kernel (odd K-step count, M <= 32) */
+  int math;     /* the math of the kernel launched (msl_conv_form.math; the tile kernel is exact f32) */
+  int tiles_m, tiles_n, ksteps; /* output tiles, K-steps (one tap, 16 channels each) */
+  int kps, S;   /* stream-K: LDS stages per tile, 1; tile kernel: K-steps per slab, slabs */
+  int tdp, NW, T; /* stream-K schedule: tiles run whole (data-parallel rounds), workers of the split
+                     remainder and its stage count (0 0 0 for the tile kernel) */
+  int reduce;    /* a reduce launch follows (split tiles / slabs) */
+  int split_img; /* the image operand is pre-split by a launch of its own first */
+  int status;    /* what the call returns given a sufficient workspace: MSL_OK or MSL_ERR_SHAPE */
+} msl_conv_fwd_plan_info;
+/* family: 0 the fp32 entry points (forms->f32_form), 1 _bf16, 2 _f16.  taps 9 (dil0 >= 1, nbranch 1 or 2)
+ * or 1 (dil0 = 0, nbranch 1); cimg = channels of the image operand and M = output rows (forward: cin,
+ * cout; data gradient: cout, cin); P = nimg*h*w; accumulate as msl_pconv_dgrad_acc (1 for the masked
+ * residual too).  MSL_ERR_ARG on anything else, incl. forms the family cannot run. */
+int msl_conv_fwd_plan(int family, int nbranch, int taps, int cimg, int M, int P, int accumulate, int dil0,
+                      const msl_forms* forms, msl_conv_fwd_plan_info* out);
+
+/* ------------------------------------------------------------------------
  * Bilinear upsample, align_corners=True (F.interpolate at deeplab_multi.py:124,
  * :128).  The forward reproduces torch-CPU's rounding bit for bit.
  * ---------------------------------------------------------------------- */

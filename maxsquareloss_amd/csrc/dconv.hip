@@ -578,6 +578,19 @@ static SkKernel* sk_kernel(const SkForm& f) {
   return nullptr;
 }
 
+// The shapes a planned call refuses (MSL_ERR_SHAPE), for launch_fwd_form and the plan query
+// (msl_conv_fwd_plan) alike: the split-K tile kernel (odd K-step count, M <= 32) has no bf16 form and no
+// accumulate epilogue; the stream-K kernels index in 32 bits (the bound of 128-row tiles, for the 256-row
+// ones too), and a form without a row in kSkKernels is not built.
+static int fwd_refusal(int math, const FwdPlan& pl, int cimg, int M, int P, int accum) {
+  if (!pl.sk) return (math == kMathBf16 || accum) ? MSL_ERR_SHAPE : MSL_OK;
+  const long long lda = pad_to(M, kPackPad);
+  if ((long long)cdiv(M, std::min(pl.form.bm, 128)) * pl.tiles_n * pl.kps * kSkNW >= (1LL << 31) ||
+      (long long)cimg * P >= (1LL << 29) || (long long)pl.ksteps * kCB * lda >= (1LL << 29))
+    return MSL_ERR_SHAPE;
+  return sk_kernel(pl.form) ? MSL_OK : MSL_ERR_SHAPE;
+}
+
 // Plan, then launch in this order: k_absmax, k_split_img, the GEMM, k_sk_reduce
 static int launch_fwd_form(int math, const FwdCall& c, const msl_forms* forms, void* ws, size_t ws_bytes,
                            hipStream_t st) {
@@ -585,6 +598,7 @@ static int launch_fwd_form(int math, const FwdCall& c, const msl_forms* forms, v
   const int P = g.nimg * g.h * g.w;
   const FwdPlan pl = plan_fwd(math, g.nbranch, g.taps, c.cimg, c.M, P, c.accum, g.dil0, forms);
   if (ws_bytes < fwd_ws_bytes(pl, g.taps, c.cimg, c.M, P)) return MSL_ERR_WORKSPACE;
+  if (const int refused = fwd_refusal(math, pl, c.cimg, c.M, P, c.accum)) return refused;
   FwdArgs a{};
   a.A = c.packed;
   a.B = c.img;
@@ -610,8 +624,6 @@ static int launch_fwd_form(int math, const FwdCall& c, const msl_forms* forms, v
   a.accni = c.res_nimg;
   const dim3 block(256);
   if (!pl.sk) {
-    // the split-K tile kernel (odd K-step count, M <= 32) has no bf16 form and no accumulate epilogue
-    if (math == kMathBf16 || c.accum) return MSL_ERR_SHAPE;
     if (pl.S > 1) {
       a.C = (float*)ws;
       a.bias = nullptr;
@@ -628,12 +640,7 @@ static int launch_fwd_form(int math, const FwdCall& c, const msl_forms* forms, v
     return MSL_OK;
   }
   const SkForm& f = pl.form;
-  // 32-bit index arithmetic in the kernel (the bound of 128-row tiles, for the 256-row ones too)
-  if ((long long)cdiv(c.M, std::min(f.bm, 128)) * pl.tiles_n * pl.kps * kSkNW >= (1LL << 31) ||
-      (long long)c.cimg * P >= (1LL << 29) || (long long)pl.ksteps * kCB * a.lda >= (1LL << 29))
-    return MSL_ERR_SHAPE;
   SkKernel* k = sk_kernel(f);
-  if (!k) return MSL_ERR_SHAPE;
   SkArgs sk = pl.sched;
   sk.part = (float*)ws;
   const long long tiles = (long long)pl.tiles_m * pl.tiles_n;
@@ -1201,6 +1208,48 @@ int msl_conv_wgrad_split(int nbranch, int taps, int cin, int cout, int h, int w,
   const int wr = taps == 1 ? P : w;  // a pointwise call passes one flat row (msl_pconv_wgrad*)
   if (wgrad_swaps(nbranch, taps, cin, cout) && plan_wgrad(nbranch, taps, cout, cin, P, true, wr).rx6) return 1;
   return plan_wgrad(nbranch, taps, cin, cout, P, true, wr).rx6 ? 1 : 0;
+}
+
+int msl_conv_fwd_form_count(void) { return (int)(sizeof(kSkKernels) / sizeof(kSkKernels[0])); }
+
+int msl_conv_fwd_form_describe(int row, msl_conv_form* out) {
+  if (row < 0 || row >= msl_conv_fwd_form_count() || !out) return MSL_ERR_ARG;
+  const SkForm& f = kSkKernels[row].form;
+  *out = {f.bm, f.G, f.stages, f.wm, f.wn, f.pw ? 1 : 0, f.mt, f.acc ? 1 : 0, f.bform};
+  return MSL_OK;
+}
+
+int msl_conv_fwd_plan(int family, int nbranch, int taps, int cimg, int M, int P, int accumulate, int dil0,
+                      const msl_forms* forms, msl_conv_fwd_plan_info* out) {
+  if (family < kFamF32 || family > kFamF16 || !out) return MSL_ERR_ARG;
+  const int math = family_math((Family)family, forms);
+  // the geometries of the entry points: 3x3 with a dilation (one or two branches), one unshifted pointwise tap
+  if (math < 0 || bad_dims(nbranch, cimg, M, 1, 1) || P < 1 || P > (1 << 30) ||
+      !((taps == 9 && dil0 >= 1) || (taps == 1 && dil0 == 0 && nbranch == 1)))
+    return MSL_ERR_ARG;
+  const int accum = accumulate ? 1 : 0;
+  const FwdPlan pl = plan_fwd(math, nbranch, taps, cimg, M, P, accum, dil0, forms);
+  msl_conv_fwd_plan_info info{};
+  info.row = -1;
+  info.stream_k = pl.sk ? 1 : 0;
+  info.math = kMathF32;  // the split-K tile kernel is exact f32 in every family
+  info.tiles_m = pl.tiles_m;
+  info.tiles_n = pl.tiles_n;
+  info.ksteps = pl.ksteps;
+  info.kps = pl.kps;
+  info.S = pl.S;
+  info.reduce = pl.sk ? (pl.reduce ? 1 : 0) : (pl.S > 1 ? 1 : 0);
+  info.status = fwd_refusal(math, pl, cimg, M, P, accum);
+  if (pl.sk) {
+    if (SkKernel* k = sk_kernel(pl.form)) info.row = (int)(k - kSkKernels);
+    info.math = pl.form.mt;
+    info.tdp = pl.sched.tdp;
+    info.NW = pl.sched.NW;
+    info.T = pl.sched.T;
+    info.split_img = pl.form.bform == kBPre ? 1 : 0;
+  }
+  *out = info;
+  return MSL_OK;
 }
 
 int msl_absmax_partials(const float* x, int rows, int row_len, float* part, msl_stream_t stream) {

@@ -57,6 +57,9 @@ SIGNATURES = {
     "msl_pconv_dgrad_f16": (c_int, [c_p] * 3 + [c_int] * 4 + [c_p, c_p, c_sz, c_p, c_p, c_int]),
     "msl_pconv_wgrad_f16": (c_int, [c_p] * 3 + [c_int] * 4 + [c_p, c_p, c_sz, c_p, c_p, c_int, c_p, c_int]),
     "msl_conv_wgrad_split": (c_int, [c_int] * 7),
+    "msl_conv_fwd_form_count": (c_int, []),
+    "msl_conv_fwd_form_describe": (c_int, [c_int, c_p]),
+    "msl_conv_fwd_plan": (c_int, [c_int] * 8 + [c_p, c_p]),
     "msl_dconv_fwd_bf16": (c_int, [c_p, c_p, c_p, c_p] + [c_int] * 8 + [c_p, c_p, c_sz, c_p]),
     "msl_dconv_dgrad_bf16": (c_int, [c_p, c_p, c_p] + [c_int] * 8 + [c_p, c_p, c_sz, c_p]),
     "msl_dconv_wgrad_bf16": (c_int, [c_p, c_p, c_p, c_p] + [c_int] * 9 + [c_p, c_p, c_sz, c_p]),
@@ -193,6 +196,26 @@ def ptr(t):
 class Forms(ctypes.Structure):
     """msl_forms (include/msl_hip.h): the kernel forms every conv / pack / BN call takes (ABI 3)."""
     _fields_ = [("f32_form", c_int), ("sk_hybrid", c_int), ("pack_form", c_int), ("bn_fused", c_int)]
+
+
+class ConvForm(ctypes.Structure):
+    """msl_conv_form: one instantiation of the stream-K forward-form kernel (msl_conv_fwd_form_describe)."""
+    _fields_ = [(n, c_int) for n in ("bm", "G", "stages", "wm", "wn", "pw", "math", "acc", "bform")]
+
+
+class ConvFwdPlan(ctypes.Structure):
+    """msl_conv_fwd_plan_info: the plan of one forward-form call (msl_conv_fwd_plan; host only)."""
+    _fields_ = [(n, c_int) for n in ("row", "stream_k", "math", "tiles_m", "tiles_n", "ksteps", "kps", "S", "tdp",
+                                     "NW", "T", "reduce", "split_img", "status")]
+
+
+def conv_fwd_plan(family, nbranch, taps, cimg, m, p, accumulate, dil0, forms_=None):
+    """The plan of a forward-form call as a ConvFwdPlan (no GPU needed); `forms_` defaults to FORMS."""
+    out = ConvFwdPlan()
+    fm = forms() if forms_ is None else ctypes.addressof(forms_)
+    check(load(require_gpu=False).msl_conv_fwd_plan(family, nbranch, taps, cimg, m, p, accumulate, dil0, fm,
+                                                    ctypes.addressof(out)), "msl_conv_fwd_plan")
+    return out
 
 
 FORMS = Forms(5, 1, 1, 1)  # the forms this process passes: the library's defaults until set_form

@@ -54,7 +54,9 @@ def test_launch_guard_refuses_oversized_blocks():
 
 @pytest.mark.parametrize("cin,cout,h,w,d", [
     (256, 256, 17, 33, 2), (512, 512, 17, 33, 4), (64, 64, 33, 65, 1), (32, 48, 9, 13, 2),
-    (256, 256, 65, 129, 2)])
+    (256, 256, 65, 129, 2),
+    # w < 16: the weight gradient's register-staged split kernel is refused and the 128-row stream-K tiles run
+    (256, 256, 21, 13, 2)])
 def test_dconv_fwd_bwd(cin, cout, h, w, d, f32_form):
     g = torch.Generator().manual_seed(cin * 7 + h)
     x = torch.randn(1, cin, h, w, generator=g)
@@ -152,6 +154,22 @@ def test_aspp_shift_form_matches_direct(cin, c, h, w, n, d0, d1, monkeypatch):
     """The r04 shift form of the heads (one pointwise GEMM with 18*C rows, then shifts: csrc/aspp.hip)
     against the two-branch implicit GEMM (ASPP_FORM = "direct") on pairs and single images, incl. maps
     narrower / shorter than the dilation (every tap of some pixels falls outside its image)."""
+    _aspp_shift_vs_direct(cin, c, h, w, n, d0, d1, monkeypatch)
+
+
+@pytest.mark.parametrize("form", ["mfma_f32", "bf16x6"])
+@pytest.mark.parametrize("cin,c,h,w,n,d0,d1", [(256, 19, 9, 17, 1, 6, 12), (128, 5, 13, 7, 2, 2, 5)])
+def test_aspp_shift_form_matches_direct_f32_forms(cin, c, h, w, n, d0, d1, form, monkeypatch):
+    """The same on the small shapes in the other two fp32 forms (above: f16x3, the default), where the direct
+    two-branch GEMM with M <= 32 runs the 32-row exact-f32 stream-K tiles that f16x3 promotes to 64 rows."""
+    prev = ops.set_f32_form(form)
+    try:
+        _aspp_shift_vs_direct(cin, c, h, w, n, d0, d1, monkeypatch)
+    finally:
+        ops.set_f32_form(prev)
+
+
+def _aspp_shift_vs_direct(cin, c, h, w, n, d0, d1, monkeypatch):
     g = torch.Generator().manual_seed(cin + c + h)
     shape = (1, cin, n, h, w) if n > 1 else (1, cin, h, w)
     x = torch.randn(shape, generator=g).to(DEV)
@@ -496,12 +514,13 @@ def _f16(t):
 @pytest.mark.parametrize("kind,cin,cout,h,w,d", [
     ("dconv", 256, 256, 17, 33, 2), ("dconv", 512, 512, 17, 33, 4), ("dconv", 64, 64, 33, 65, 1),
     ("pconv", 256, 1024, 17, 33, 0), ("pconv", 1024, 256, 17, 33, 0), ("pconv", 256, 64, 33, 65, 0),
-    ("pconv", 64, 256, 33, 65, 0)])
+    ("pconv", 64, 256, 33, 65, 0), ("dconv", 256, 256, 21, 13, 2)])
 def test_conv_fp16_math(kind, cin, cout, h, w, d):
     """BASELINE config 5's fp16 MFMA path (msl_*_f16): products of fp16-rounded, per-tensor scaled
     operands summed in fp32 - the forward and data gradient on every M (r04: the M <= 64 GEMMs on the
-    64-row fp16 tiles too), the weight gradient where both sides have >= 128 channels, exact f32 MFMA
-    below.  Reference: the same conv in fp64 on the operands as
+    64-row fp16 tiles too), the weight gradient where the plan runs the split kernel (msl_conv_wgrad_split:
+    both sides >= 128 channels and, for a 3x3, rows of >= 16 pixels), exact f32 MFMA
+    elsewhere.  Reference: the same conv in fp64 on the operands as
     the kernels see them, so the only admissible difference is the fp32 accumulation (1e-5 of
     max|ref|, as the fp32 kernels); operand scales far from 1 (weights 1e-2, gradients 1e-6)."""
     g = torch.Generator().manual_seed(cin + 13 * cout + d)
@@ -528,7 +547,10 @@ def test_conv_fp16_math(kind, cin, cout, h, w, d):
     def conv(xx, ww):
         return F.conv2d(xx, ww, padding=pad, dilation=dil)
 
-    rf, rd, rw = _f16, _f16, (_f16 if min(cin, cout) >= 128 else exact)
+    from maxsquareloss_amd import hip
+    split = hip.load().msl_conv_wgrad_split(1, 9 if kind == "dconv" else 1, cin, cout, h, w, 1)
+    assert split in (0, 1)
+    rf, rd, rw = _f16, _f16, (_f16 if split else exact)
     assert _rel(y, conv(rf(x), rf(wt))) < 1e-5
     xr = rd(x).requires_grad_()
     conv(xr, rd(wt)).backward(rd(gy))

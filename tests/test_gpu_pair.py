@@ -74,7 +74,9 @@ def _conv_check(fn, ref, x, weights, gy, bar):
 
 
 @pytest.mark.parametrize("cin,cout,h,w,d", [(256, 256, 17, 33, 2), (64, 64, 33, 65, 1), (512, 512, 9, 17, 4),
-                                            (128, 128, 13, 29, 2), (256, 256, 65, 129, 2)])
+                                            (128, 128, 13, 29, 2), (256, 256, 65, 129, 2),
+                                            # w < 16: the weight gradient on the 128-row stream-K tiles
+                                            (256, 256, 21, 13, 2)])
 def test_dconv_pair(cin, cout, h, w, d, f32_form):
     g = torch.Generator().manual_seed(cin + h)
     x, gy = _pair(cin, h, w, g), torch.randn(1, cout, 2, h, w, generator=g)
