@@ -598,6 +598,31 @@ int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi,
                    const long long* label, unsigned long long* confusion, int32_t* argmax_out,
                    msl_stream_t stream);
 
+/* msl_predict_up's decision written as images, in the same single pass (inputs, label / confusion and
+ * the class as there; all maps uint8, all nullable, at least one of them or the confusion matrix required):
+ *   class_out  [ho*wo]    the class, the value msl_predict_up writes to argmax_out;
+ *   ids_out    [ho*wo]    id_lut[class], id_lut a device uint8 [c] (class -> Cityscapes labelId);
+ *   color_out  [ho*wo*3]  palette[class], HWC RGB, palette a device uint8 [c*3];
+ *   conf_out   [ho*wo*3]  shade[bucket][class], shade a device uint8 [4*c*3]: bucket 0 where the winning
+ *                         probability p > 0.9, else 1 where > 0.8, else 2 where > 0.7, else 3 where > 0.5,
+ *                         else black (the splits of the reference's inspect_decode_labels);
+ *   pseudo_out [ho*wo]    the class where p > thr, else 255 (the rule of the hard target mode).
+ * p is softmax(up(logits)) at its first maximum, with logits_flip the averaged probability the class is
+ * taken from; a NaN pixel is black in conf_out and 255 in pseudo_out.  A thread writes four pixels of a
+ * row as dwords when wo % 4 == 0 and the outputs are 4-byte aligned, else bytes.  An output whose table
+ * is NULL, no output at all, label without confusion, c > 32 or a bad geometry are MSL_ERR_ARG. */
+int msl_predict_images(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                       const long long* label, unsigned long long* confusion, float thr,
+                       const uint8_t* id_lut, const uint8_t* palette, const uint8_t* shade,
+                       uint8_t* class_out, uint8_t* ids_out, uint8_t* color_out, uint8_t* conf_out,
+                       uint8_t* pseudo_out, msl_stream_t stream);
+
+/* decode_labels (datasets/cityscapes_Dataset.py:352-377) on the device: out[px] = palette[cls[px]] for
+ * the npx elements of a class map (int64 when is_int64, else int32), out uint8 [npx*3] HWC RGB, palette a
+ * device uint8 [c*3], c <= 256; values outside [0, c), -1 included, are black. */
+int msl_colorize(const void* cls, int is_int64, long long npx, const uint8_t* palette, int c, uint8_t* out,
+                 msl_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Input pipeline (the loaders' last host steps, on the device after a uint8 H2D copy; byte-exact):
  *   msl_image_transform: out[c][y][x] = (float)rgb[y][xs][2 - c] - mean[c] (BGR order, mean =

@@ -845,12 +845,34 @@ __device__ __forceinline__ int argmax_np(const float (&v)[CM], int C) {
   return a;
 }
 
-// The evaluator's per-pixel class (tools/evaluate.py:114-141) from the LOW-resolution logits, and its
-// (gt, class) cell of the confusion matrix (utils/eval.py:109-115).  FLIP = 0: np.argmax of up(L).
-// FLIP = 1: np.argmax of (softmax(up(L))[y][x] + softmax(up(Lf))[y][Wo-1-x]) / 2, Lf the logits of the
-// mirrored image (the reference flips its probabilities back after upsampling).  The histogram is
-// k_confusion's: per-block LDS counts, integer atomics on the uint64 matrix - exact in any order.
-// label / cm and arg are nullable (the host requires one of them).
+constexpr int kPredictBlocks = 1024;  // grid cap of k_predict_up / k_predict_images (grid-stride beyond it)
+
+// The evaluator's per-pixel decision (tools/evaluate.py:114-141), shared by k_predict_up and
+// k_predict_images.  FLIP = 0: v = up(L) at (ly, ox), the class is np.argmax of v.  FLIP = 1: p =
+// (softmax(up(L))[y][x] + softmax(up(Lf))[y][Wo-1-x]) / 2, Lf the logits of the mirrored image (the
+// reference flips its probabilities back after upsampling), the class is np.argmax of p; v is scratch.
+template <int FLIP, int CM>
+__device__ __forceinline__ int pixel_class(const float* __restrict__ L, const float* __restrict__ Lf,
+                                           const Geo& g, const Lin& ly, int ox, float (&v)[CM],
+                                           float (&p)[CM]) {
+  const Lin lx = lin(ox, g.sw, g.Wi);
+  up_logits<CM>(L, g, ly, lx, v);
+  if (FLIP) {
+    float q[CM], mx, sum;
+    softmax<CM>(v, g.C, p, mx, sum);
+    up_logits<CM>(Lf, g, ly, lin(g.Wo - 1 - ox, g.sw, g.Wi), v);
+    softmax<CM>(v, g.C, q, mx, sum);
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < g.C) p[c] = (p[c] + q[c]) / 2.f;
+    return argmax_np<CM>(p, g.C);
+  }
+  return argmax_np<CM>(v, g.C);
+}
+
+// The class of every hi-res pixel and its (gt, class) cell of the confusion matrix
+// (utils/eval.py:109-115).  The histogram is k_confusion's: per-block LDS counts, integer atomics on the
+// uint64 matrix - exact in any order.  label / cm and arg are nullable (the host requires one of them).
 template <int FLIP, int CM>
 __global__ void __launch_bounds__(256) k_predict_up(const float* __restrict__ L,
                                                      const float* __restrict__ Lf, Geo g,
@@ -867,22 +889,9 @@ __global__ void __launch_bounds__(256) k_predict_up(const float* __restrict__ L,
   for (long long pp = blockIdx.x * 256LL + threadIdx.x; pp < npx; pp += (long long)gridDim.x * 256) {
     const int px = (int)pp;
     const int oy = px / g.Wo, ox = px - oy * g.Wo;
-    const Lin ly = lin(oy, g.sh, g.Hi), lx = lin(ox, g.sw, g.Wi);
-    float v[CM];
-    up_logits<CM>(L, g, ly, lx, v);
-    int best;
-    if (FLIP) {
-      float p[CM], q[CM], mx, sum;
-      softmax<CM>(v, g.C, p, mx, sum);
-      up_logits<CM>(Lf, g, ly, lin(g.Wo - 1 - ox, g.sw, g.Wi), v);
-      softmax<CM>(v, g.C, q, mx, sum);
-#pragma unroll
-      for (int c = 0; c < CM; ++c)
-        if (c < g.C) p[c] = (p[c] + q[c]) / 2.f;
-      best = argmax_np<CM>(p, g.C);
-    } else {
-      best = argmax_np<CM>(v, g.C);
-    }
+    const Lin ly = lin(oy, g.sh, g.Hi);
+    float v[CM], p[CM];
+    const int best = pixel_class<FLIP, CM>(L, Lf, g, ly, ox, v, p);
     if (arg) arg[px] = best;
     if (cm) {
       const long long y = label[px];
@@ -893,6 +902,169 @@ __global__ void __launch_bounds__(256) k_predict_up(const float* __restrict__ L,
     __syncthreads();
     for (int i = threadIdx.x; i < cc; i += 256)
       if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
+  }
+}
+
+// ---------------------------------------------------------------- evaluation: prediction images
+struct ImgOut {
+  uint8_t* cls;     // [Ho*Wo]   the class (k_predict_up's arg as a byte)
+  uint8_t* ids;     // [Ho*Wo]   id_lut[class]
+  uint8_t* color;   // [Ho*Wo*3] palette[class], HWC
+  uint8_t* conf;    // [Ho*Wo*3] shade[bucket of the winning probability][class], black below 0.5
+  uint8_t* pseudo;  // [Ho*Wo]   class where the winning probability > thr, else 255
+};
+
+__device__ __forceinline__ unsigned int rgb24(const uint8_t* __restrict__ t, int i) {
+  return (unsigned int)t[3 * i] | ((unsigned int)t[3 * i + 1] << 8) | ((unsigned int)t[3 * i + 2] << 16);
+}
+
+// four 24-bit pixels -> the three dwords of their 12 bytes
+__device__ __forceinline__ void store_rgb4(uint8_t* __restrict__ out, long long quad, unsigned int a,
+                                           unsigned int b, unsigned int c, unsigned int d) {
+  unsigned int* o = reinterpret_cast<unsigned int*>(out) + 3 * quad;
+  o[0] = a | (b << 24);
+  o[1] = (b >> 8) | (c << 16);
+  o[2] = (c >> 16) | (d << 8);
+}
+
+__device__ __forceinline__ void store_rgb1(uint8_t* __restrict__ out, long long px, unsigned int a) {
+  out[3 * px] = (uint8_t)a;
+  out[3 * px + 1] = (uint8_t)(a >> 8);
+  out[3 * px + 2] = (uint8_t)(a >> 16);
+}
+
+// k_predict_up's decision written as images.  A thread takes four consecutive pixels of one row (a
+// quad), one after the other (the registers are those of one pixel), and keeps their bytes in
+// registers: with VEC (Wo % 4 == 0 and dword-aligned outputs, so quad q is bytes [4q, 4q+4) of a byte
+// map and [12q, 12q+12) of an RGB map) it stores one dword per byte map and three per RGB map; without,
+// rows are not dword-aligned, the last quad of a row is partial and every pixel stores its own bytes.
+// The tables sit in LDS as one dword per entry.  The winning probability is that of argmax_first over
+// p (no flip: softmax(up(L)); flip: the averaged p) and the pseudo-label decision is hard_label's.
+template <int FLIP, int CM>
+__global__ void __launch_bounds__(256) k_predict_images(const float* __restrict__ L,
+                                                         const float* __restrict__ Lf, Geo g,
+                                                         const long long* __restrict__ label,
+                                                         unsigned long long* __restrict__ cm, float thr,
+                                                         const uint8_t* __restrict__ id_lut,
+                                                         const uint8_t* __restrict__ palette,
+                                                         const uint8_t* __restrict__ shade, ImgOut o,
+                                                         int vec) {
+  __shared__ unsigned int h[kMaxC * kMaxC];
+  __shared__ unsigned int t_pal[kMaxC], t_id[kMaxC], t_shade[4 * kMaxC];
+  const int cc = g.C * g.C;
+  if (cm)
+    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
+  if ((int)threadIdx.x < g.C) {
+    t_pal[threadIdx.x] = palette ? rgb24(palette, threadIdx.x) : 0u;
+    t_id[threadIdx.x] = id_lut ? id_lut[threadIdx.x] : 0u;
+  }
+  if ((int)threadIdx.x < 4 * g.C) t_shade[threadIdx.x] = shade ? rgb24(shade, threadIdx.x) : 0u;
+  __syncthreads();
+  const bool want_p = o.conf || o.pseudo;
+  const int nq = (g.Wo + 3) >> 2;                   // quads per row
+  const long long nquad = (long long)g.Ho * nq;     // < 2^31 (geo_ok)
+  for (long long qq = blockIdx.x * 256LL + threadIdx.x; qq < nquad; qq += (long long)gridDim.x * 256) {
+    const int q = (int)qq;
+    const int oy = q / nq, ox0 = (q - oy * nq) << 2;
+    const int row = oy * g.Wo;
+    unsigned int w_cls = 0u, w_ids = 0u, w_ps = 0u;
+    unsigned int c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u, f0 = 0u, f1 = 0u, f2 = 0u, f3 = 0u;
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int ox = ox0 + j;
+      if (ox >= g.Wo) break;  // never with vec
+      // the row's taps are the same for the four pixels, but hoisted out of the loop they are 2 * CM row
+      // pointers held in VGPRs across it (168 VGPRs at C = 19 against k_predict_up's 45): recompute them
+      // per pixel from a row index the compiler cannot see through
+      int oyj = oy;
+      asm volatile("" : "+v"(oyj));
+      const Lin ly = lin(oyj, g.sh, g.Hi);
+      float v[CM], p[CM];
+      const int best = pixel_class<FLIP, CM>(L, Lf, g, ly, ox, v, p);
+      const int px = row + ox;
+      if (cm) {
+        const long long y = label[px];
+        if (y >= 0 && y < g.C) atomicAdd(&h[(int)y * g.C + best], 1u);
+      }
+      unsigned int ps = 255u, cf = 0u;
+      if (want_p) {
+        if (!FLIP) {
+          float mx, sum;
+          softmax<CM>(v, g.C, p, mx, sum);
+        }
+        float top;
+        argmax_first<CM>(p, g.C, top);
+        if (hard_label<CM>(p, g.C, thr) >= 0) ps = (unsigned int)best;
+        const int bucket = top > 0.9f ? 0 : top > 0.8f ? 1 : top > 0.7f ? 2 : top > 0.5f ? 3 : -1;
+        if (bucket >= 0) cf = t_shade[bucket * g.C + best];
+      }
+      const unsigned int col = t_pal[best], id = t_id[best];
+      if (vec) {
+        const int sh = 8 * j;
+        w_cls |= (unsigned int)best << sh;
+        w_ids |= id << sh;
+        w_ps |= ps << sh;
+        c0 = j == 0 ? col : c0;
+        c1 = j == 1 ? col : c1;
+        c2 = j == 2 ? col : c2;
+        c3 = j == 3 ? col : c3;
+        f0 = j == 0 ? cf : f0;
+        f1 = j == 1 ? cf : f1;
+        f2 = j == 2 ? cf : f2;
+        f3 = j == 3 ? cf : f3;
+      } else {
+        if (o.cls) o.cls[px] = (uint8_t)best;
+        if (o.ids) o.ids[px] = (uint8_t)id;
+        if (o.pseudo) o.pseudo[px] = (uint8_t)ps;
+        if (o.color) store_rgb1(o.color, px, col);
+        if (o.conf) store_rgb1(o.conf, px, cf);
+      }
+    }
+    if (vec) {  // row + ox0 == 4 * q
+      if (o.cls) reinterpret_cast<unsigned int*>(o.cls)[q] = w_cls;
+      if (o.ids) reinterpret_cast<unsigned int*>(o.ids)[q] = w_ids;
+      if (o.pseudo) reinterpret_cast<unsigned int*>(o.pseudo)[q] = w_ps;
+      if (o.color) store_rgb4(o.color, q, c0, c1, c2, c3);
+      if (o.conf) store_rgb4(o.conf, q, f0, f1, f2, f3);
+    }
+  }
+  if (cm) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < cc; i += 256)
+      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
+  }
+}
+
+// decode_labels (datasets/cityscapes_Dataset.py:352-377) on the device: out[px] = palette[cls[px]], black
+// outside [0, C).  A thread takes four pixels: three dword stores with VEC (dword-aligned out), else
+// bytes; the last quad may be partial.
+constexpr int kColorizeMaxC = 256;
+template <typename T>
+__global__ void __launch_bounds__(256) k_colorize(const T* __restrict__ cls, long long npx,
+                                                   const uint8_t* __restrict__ palette, int C,
+                                                   uint8_t* __restrict__ out, int vec) {
+  __shared__ unsigned int t_pal[kColorizeMaxC];
+  for (int i = threadIdx.x; i < C; i += 256) t_pal[i] = rgb24(palette, i);
+  __syncthreads();
+  const long long nquad = (npx + 3) >> 2;
+  for (long long q = blockIdx.x * 256LL + threadIdx.x; q < nquad; q += (long long)gridDim.x * 256) {
+    unsigned int col[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long px = 4 * q + j;
+      col[j] = 0u;
+      if (px < npx) {
+        const long long k = (long long)cls[px];
+        if (k >= 0 && k < C) col[j] = t_pal[(int)k];
+      }
+    }
+    if (vec && 4 * q + 3 < npx) {
+      store_rgb4(out, q, col[0], col[1], col[2], col[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * q + j < npx) store_rgb1(out, 4 * q + j, col[j]);
+    }
   }
 }
 
@@ -1207,7 +1379,7 @@ int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi,
       (!confusion && !argmax_out))
     return MSL_ERR_ARG;
   const Geo g = make_geo(c, hi, wi, ho, wo);
-  const int nblk = std::min(1024, cdiv((long long)ho * wo, 256));
+  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * wo, 256));
   hipStream_t st = as_stream(stream);
   if (logits_flip)
     MSL_DISPATCH_C(c, CM,
@@ -1217,6 +1389,53 @@ int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi,
     MSL_DISPATCH_C(c, CM,
                    MSL_LAUNCH((k_predict_up<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
                               g, label, confusion, argmax_out));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+static bool dword_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+int msl_predict_images(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                       const long long* label, unsigned long long* confusion, float thr,
+                       const uint8_t* id_lut, const uint8_t* palette, const uint8_t* shade,
+                       uint8_t* class_out, uint8_t* ids_out, uint8_t* color_out, uint8_t* conf_out,
+                       uint8_t* pseudo_out, msl_stream_t stream) {
+  const bool any_out = class_out || ids_out || color_out || conf_out || pseudo_out;
+  if (!geo_ok(c, hi, wi, ho, wo) || !logits || (label == nullptr) != (confusion == nullptr) ||
+      (!confusion && !any_out) || (ids_out && !id_lut) || (color_out && !palette) || (conf_out && !shade))
+    return MSL_ERR_ARG;
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  const ImgOut o = {class_out, ids_out, color_out, conf_out, pseudo_out};
+  const int vec = wo % 4 == 0 && dword_aligned(class_out) && dword_aligned(ids_out) &&
+                  dword_aligned(color_out) && dword_aligned(conf_out) && dword_aligned(pseudo_out);
+  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * cdiv(wo, 4), 256));
+  hipStream_t st = as_stream(stream);
+  if (logits_flip)
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_predict_images<1, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
+                              g, label, confusion, thr, id_lut, palette, shade, o, vec));
+  else
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_predict_images<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
+                              g, label, confusion, thr, id_lut, palette, shade, o, vec));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_colorize(const void* cls, int is_int64, long long npx, const uint8_t* palette, int c, uint8_t* out,
+                 msl_stream_t stream) {
+  if (!cls || !palette || !out || npx < 0 || c < 1 || c > kColorizeMaxC || (is_int64 != 0 && is_int64 != 1))
+    return MSL_ERR_ARG;
+  if (npx == 0) return MSL_OK;
+  const int vec = dword_aligned(out);
+  const int nblk = (int)std::min<long long>(4096, (npx + 1023) / 1024);
+  hipStream_t st = as_stream(stream);
+  if (is_int64)
+    MSL_LAUNCH((k_colorize<long long>), dim3(nblk), dim3(256), 0, st, (const long long*)cls, npx, palette, c,
+               out, vec);
+  else
+    MSL_LAUNCH((k_colorize<int32_t>), dim3(nblk), dim3(256), 0, st, (const int32_t*)cls, npx, palette, c, out,
+               vec);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

@@ -2,7 +2,7 @@
 datasets/gta5_Dataset.py): PNGs decoded by Pillow on the host, everything after the decode -
 mirror, crop, BICUBIC / NEAREST resize, BGR - mean, id -> trainId - on the device, byte-exact
 (utils/preprocess.py resize_image / resize_label)."""
-from .cityscapes_Dataset import City_DataLoader, City_Dataset, DeviceLoader  # noqa: F401
+from .cityscapes_Dataset import City_DataLoader, City_Dataset, Client_dataset, DeviceLoader  # noqa: F401
 from .gta5_Dataset import GTA5_DataLoader, GTA5_Dataset  # noqa: F401
 
 

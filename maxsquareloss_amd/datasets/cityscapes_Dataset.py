@@ -23,9 +23,12 @@ import torch
 
 from ..hip import MSLError
 from ..utils import preprocess, resample
+from ..utils.eval import name_classes  # noqa: F401  (the reference keeps the row names in this module)
+from ..utils.palette import label_colours, palette_table
 from ..utils.synthetic import IMG_MEAN
 
 MAX_WORKERS = 16
+NUM_CLASSES = 19
 
 
 def _pil():
@@ -172,6 +175,9 @@ class _Slot:
             self.event.synchronize()
         out = []
         for name, arr in (("rgb", rgb), ("ids", ids)):
+            if arr is None:  # an unlabelled item (Client_dataset)
+                out.append(None)
+                continue
             buf = getattr(self, name)
             if buf is None or buf.numel() < arr.size:
                 buf = torch.empty(arr.size, dtype=torch.uint8).pin_memory()
@@ -242,7 +248,7 @@ class DeviceLoader:
         dev = ds._device()
         for rgb, ids, plan, ident, slot in self.host_items(staged=True):
             d_rgb = rgb.to(dev, non_blocking=True)
-            d_ids = ids.to(dev, non_blocking=True)
+            d_ids = ids.to(dev, non_blocking=True) if ids is not None else None
             slot.event = torch.cuda.Event()
             slot.event.record(torch.cuda.current_stream(dev))
             img, lab = ds.device_transform(d_rgb, d_ids, plan)
@@ -297,3 +303,110 @@ class City_DataLoader:
     def close(self):
         self.data_loader.close()
         self.val_loader.close()
+
+
+class Client_dataset:
+    """cityscapes_Dataset.py:43-83: a list of unlabelled images to predict on.  `<list_path>/test.txt`
+    holds one image path per line; with --resize the image is resized to seg_size (Pillow's BICUBIC,
+    byte-exact on the device) before the image transform.  Items are (image (1,3,H,W) fp32, None, name),
+    name the list entry's base name without its extension.  Decodes ahead through DeviceLoader like the
+    labelled datasets."""
+    name = "client"
+
+    def __init__(self, dataset_path, args):
+        self.args, self.dataset_path = args, dataset_path
+        self.resize = bool(getattr(args, "resize", False))
+        self.rsize = _pair(args.seg_size) if self.resize else None
+        path = os.path.join(dataset_path["list_path"], "test.txt")
+        if not os.path.exists(path):
+            raise MSLError(f"Client_dataset: list file {path} is missing")
+        with open(path) as f:
+            self.items = [line.strip() for line in f if line.strip()]
+        self.device = None
+
+    def __len__(self):
+        return len(self.items)
+
+    def paths(self, item):
+        path = self.items[item]
+        return path, None, os.path.splitext(os.path.basename(path))[0]
+
+    def decode(self, item):
+        Image = _pil()
+        with Image.open(self.paths(item)[0]) as im:
+            return np.asarray(im.convert("RGB"), np.uint8), None
+
+    def plan(self, w, h):
+        return False, [(self.rsize if self.resize else (w, h), None)]
+
+    def device_transform(self, rgb, ids, plan):
+        mirror, steps = plan
+        return preprocess.resize_image(rgb, steps[0][0], None, mirror), None
+
+    _device = City_Dataset._device
+
+    def __getitem__(self, item):
+        rgb, _ = self.decode(item)
+        img, _ = self.device_transform(torch.from_numpy(rgb).to(self._device()), None,
+                                       self.plan(rgb.shape[1], rgb.shape[0]))
+        return img, None, self.paths(item)[2]
+
+
+# ---------------------------------------------------------------------- looking at images and predictions
+def _palette_of(num_classes):
+    """uint8 [C, 3]: the colour of every class - through its trainId for the 16- and 13-class sets (a
+    deviation from the reference, which paints class index k with colour k whatever the class count; the
+    same for 19 classes), the first num_classes colours otherwise."""
+    if num_classes in (19, 16, 13):
+        return palette_table(num_classes)
+    if not 1 <= num_classes <= len(label_colours):
+        raise MSLError(f"decode_labels: no colours for {num_classes} classes")
+    return np.array(label_colours[:num_classes], np.uint8)
+
+
+_DEVICE_PALETTES = {}
+
+
+def decode_labels(mask, num_images=1, num_classes=NUM_CLASSES):
+    """cityscapes_Dataset.py:352-377: the first min(n, num_images) class maps of `mask` (n, h, w) as colour
+    images, a float (n', 3, h, w) tensor in [0, 1]; values outside [0, num_classes), the ignored -1
+    included, are black.  A device tensor is coloured on the device (msl_colorize) and the result stays
+    there; numpy arrays and CPU tensors are coloured with numpy."""
+    if torch.is_tensor(mask) and mask.is_cuda:
+        from .. import ops
+        n = min(int(mask.shape[0]), int(num_images))
+        key = (int(num_classes), mask.device)
+        if key not in _DEVICE_PALETTES:
+            # the byte -> float table is divided on the host: the device's fp32 division by 255 rounds some
+            # bytes one ulp away from the reference's
+            _DEVICE_PALETTES[key] = (torch.from_numpy(_palette_of(int(num_classes))).to(mask.device),
+                                     torch.arange(256, dtype=torch.float32).div_(255.0).to(mask.device))
+        pal, unit = _DEVICE_PALETTES[key]
+        m = mask[:n]
+        if m.dtype not in (torch.int64, torch.int32):
+            m = m.to(torch.int64)
+        return unit[ops.colorize(m, pal).permute(0, 3, 1, 2).long()]
+    if torch.is_tensor(mask):
+        mask = mask.data.cpu().numpy()
+    mask = np.asarray(mask)
+    n = min(mask.shape[0], int(num_images))
+    m = mask[:n].astype(np.int64)
+    pal = np.concatenate([_palette_of(int(num_classes)), np.zeros((1, 3), np.uint8)])
+    outputs = pal[np.where((m >= 0) & (m < num_classes), m, len(pal) - 1)]
+    return torch.from_numpy(outputs.transpose([0, 3, 1, 2]).astype("float32")).div_(255.0)
+
+
+def inv_preprocess(imgs, num_images=1, img_mean=IMG_MEAN, numpy_transform=False):
+    """cityscapes_Dataset.py:332-350: the network input as something to look at - with numpy_transform
+    the channels flipped back (BGR -> RGB), then the whole batch normalised to [0, 1) by its own minimum
+    and maximum, (x - min) / (max - min + 1e-5).  As in the reference num_images and img_mean are not
+    read and, without the channel flip, `imgs` is normalised in place.  Torch ops on the tensor's own
+    device; numpy input is accepted."""
+    if not torch.is_tensor(imgs):
+        imgs = torch.from_numpy(np.asarray(imgs))
+    if numpy_transform:
+        imgs = imgs.flip(1)
+    lo, hi = float(imgs.min()), float(imgs.max())
+    imgs.clamp_(min=lo, max=hi)
+    imgs.add_(-lo).div_(hi - lo + 1e-5)
+    return imgs

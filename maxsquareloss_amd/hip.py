@@ -97,6 +97,8 @@ SIGNATURES = {
     "msl_iw_maxsquare_prob_bwd": (c_int, [c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
     "msl_confusion_accumulate": (c_int, [c_p, c_p, c_int, ctypes.c_longlong, c_p, c_p, c_p]),
     "msl_predict_up": (c_int, [c_p, c_p] + [c_int] * 5 + [c_p, c_p, c_p, c_p]),
+    "msl_predict_images": (c_int, [c_p, c_p] + [c_int] * 5 + [c_p, c_p, c_f] + [c_p] * 9),
+    "msl_colorize": (c_int, [c_p, c_int, c_ll, c_p, c_int, c_p, c_p]),
     "msl_bn_uses_fused": (c_int, [c_int, c_int, c_int, c_p]),
     "msl_bn_workspace": (c_sz, [c_int] * 3),
     "msl_bn_fwd": (c_int, [c_p] * 10 + [c_int] * 5 + [c_f, c_f, c_int, c_p, c_p, c_sz, c_p]),
@@ -141,7 +143,9 @@ SIGNATURES = {
 ABI_VERSION = 3
 # r06 entry points an older build (MSL_LIB_PATH, a same-box A/B) may lack: the diagnostics probe and the masked
 # residual dgrad (ops.py falls back to the materialised residual gradient without it)
-_DIAGNOSTIC = {"msl_launch_guard_probe", "msl_pconv_dgrad_resmask_sc", "msl_pconv_dgrad_resmask_f16"}
+# and the prediction-image entry points (ops.predict_images / ops.colorize raise without them)
+_DIAGNOSTIC = {"msl_launch_guard_probe", "msl_pconv_dgrad_resmask_sc", "msl_pconv_dgrad_resmask_f16",
+               "msl_predict_images", "msl_colorize"}
 _lib = None
 
 

@@ -1320,6 +1320,90 @@ def predict_up(low, out_hw, low_flip=None, label=None, confusion=None, want_argm
     return arg
 
 
+# the maps of predict_images: name -> trailing shape after (ho, wo)
+IMAGE_MAPS = {"class": (), "ids": (), "color": (3,), "confidence": (3,), "pseudo": ()}
+_IMAGE_TABLES = {}  # (num_classes, device) -> (id_lut [C], palette [C*3], shade [4*C*3]) uint8 on the device
+
+
+def image_tables(num_classes, device):
+    """The three device tables of msl_predict_images (utils/palette.py), built once per class count."""
+    key = (int(num_classes), torch.device(device))
+    if key not in _IMAGE_TABLES:
+        from .utils import palette
+        try:
+            host = (palette.id_table(key[0]), palette.palette_table(key[0]), palette.shade_table(key[0]))
+        except ValueError as e:
+            raise hip.MSLError(str(e)) from e
+        _IMAGE_TABLES[key] = tuple(torch.from_numpy(t.reshape(-1).copy()).to(key[1]) for t in host)
+    return _IMAGE_TABLES[key]
+
+
+def image_buffers(out_hw, want, device):
+    """Empty uint8 outputs of predict_images for the maps in `want` (static buffers of a captured graph)."""
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    bad = [k for k in want if k not in IMAGE_MAPS]
+    if bad:
+        raise hip.MSLError(f"predict_images: unknown maps {bad}; choose from {sorted(IMAGE_MAPS)}")
+    return {k: torch.empty((ho, wo) + IMAGE_MAPS[k], dtype=torch.uint8, device=device) for k in want}
+
+
+def predict_images(low, out_hw, low_flip=None, label=None, confusion=None, want=("color",), thr=0.95, out=None):
+    """predict_up's decision as uint8 images, in the same single launch (msl_predict_images).  `want` names
+    the maps (IMAGE_MAPS): "class" (ho,wo) the class index, "ids" (ho,wo) its Cityscapes labelId, "color"
+    (ho,wo,3) its colour, "confidence" (ho,wo,3) the colour shaded by the winning probability (> 0.9 full,
+    > 0.8, > 0.7, > 0.5, else black), "pseudo" (ho,wo) the class where that probability > `thr`, else 255.
+    `label` / `confusion` as in predict_up.  `out`: a dict of buffers from image_buffers to write into
+    (then `want` is its keys).  Returns the dict of maps."""
+    low = _check_act(low.detach(), "predict_images")
+    c, hi, wi, ho, wo = _geom(low, out_hw)
+    if low_flip is not None:
+        low_flip = _check_act(low_flip.detach(), "predict_images")
+        if low_flip.shape != low.shape:
+            raise hip.MSLError("predict_images: low_flip must have low's shape")
+    if (label is None) != (confusion is None):
+        raise hip.MSLError("predict_images: label and confusion go together")
+    if label is not None:
+        label = label.contiguous()
+        if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
+            raise hip.MSLError(f"predict_images: label must be a CUDA int64 tensor with {ho * wo} elements")
+        if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
+                not confusion.is_contiguous()):
+            raise hip.MSLError(f"predict_images: confusion must be a contiguous CUDA int64 tensor with {c * c} "
+                               "elements")
+    if out is None:
+        out = image_buffers((ho, wo), want, low.device)
+    for k, t in out.items():
+        if (k not in IMAGE_MAPS or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or
+                tuple(t.shape) != (ho, wo) + IMAGE_MAPS[k]):
+            raise hip.MSLError(f"predict_images: output {k!r} must be a contiguous CUDA uint8 tensor of shape "
+                               f"{(ho, wo) + IMAGE_MAPS.get(k, ())}")
+    if not out and label is None:
+        raise hip.MSLError("predict_images: nothing to compute (no map and no label / confusion)")
+    id_lut, pal, shade = image_tables(c, low.device)
+    hip.check(hip.load().msl_predict_images(
+        low.data_ptr(), hip.ptr(low_flip), c, hi, wi, ho, wo, hip.ptr(label), hip.ptr(confusion), float(thr),
+        id_lut.data_ptr(), pal.data_ptr(), shade.data_ptr(), hip.ptr(out.get("class")), hip.ptr(out.get("ids")),
+        hip.ptr(out.get("color")), hip.ptr(out.get("confidence")), hip.ptr(out.get("pseudo")), hip.stream_ptr()),
+        "msl_predict_images")
+    return out
+
+
+def colorize(mask, palette):
+    """decode_labels on the device (msl_colorize): `mask` a CUDA int64 / int32 class map of any shape S,
+    `palette` a CUDA uint8 [C, 3]; returns uint8 S + (3,), black where the value is outside [0, C)."""
+    if not mask.is_cuda or mask.dtype not in (torch.int64, torch.int32):
+        raise hip.MSLError(f"colorize: expected a CUDA int64 or int32 class map, got {mask.dtype} {mask.device}")
+    if (not palette.is_cuda or palette.dtype != torch.uint8 or palette.dim() != 2 or palette.size(1) != 3 or
+            palette.device != mask.device):
+        raise hip.MSLError("colorize: palette must be a uint8 [C, 3] tensor on the mask's device")
+    mask, palette = mask.contiguous(), palette.contiguous()
+    out = torch.empty(tuple(mask.shape) + (3,), dtype=torch.uint8, device=mask.device)
+    hip.check(hip.load().msl_colorize(mask.data_ptr(), int(mask.dtype == torch.int64), mask.numel(),
+                                      palette.data_ptr(), palette.size(0), out.data_ptr(), hip.stream_ptr()),
+              "msl_colorize")
+    return out
+
+
 # --------------------------------------------------------------------------- soft cross-entropy, explicit target
 class _SoftCE(Function):
     """softCrossEntropy (ratio None) / IWsoftCrossEntropy on (1,C,H,W) logits and an explicit target."""

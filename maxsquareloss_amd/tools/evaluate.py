@@ -13,7 +13,11 @@ mirror through the trunk as one pair and averages the two softmaxes inside that 
 --graph True replays the per-image work as a captured hipGraph.  Differences from the reference:
 the val set is the val split of --dataset under --data_root_path (datasets/, transformed on the
 device), or without a path synthetic (--val_images items at target_crop_size); batch size 1, at most 500;
-tensorboard and image summaries are out.
+tensorboard is out.  The reference's image summaries are files here: --save_predictions DIR writes every
+item's prediction as PNGs, one sub-directory per --save_kinds entry (color, trainids, labelids,
+confidence, pseudo, input; utils/images.py) - the maps come out of that same kernel launch
+(msl_predict_images) and are encoded on --data_loader_workers host threads.  --image_summary True is
+the reference's cadence: <save_dir>/images, every 20th item and the last.
 """
 import argparse
 import logging
@@ -24,6 +28,7 @@ import torch
 from .. import ops
 from ..utils.synthetic import init_weights
 from ..utils.train_helper import get_model
+from ..utils.images import SUMMARY_EVERY, OutputRequest, parse_save_kinds
 from ..utils.validate import Validator, val_info
 from ..datasets import build_loader
 from .train_source import add_train_args, dataset_paths, init_args, str2bool
@@ -58,6 +63,11 @@ class Evaluater:
                     raise AssertionError("no pretrained_ckpt_file")
             self.load_checkpoint(path)
 
+        self.validator = self.build_validator(args)
+        self.Eval = self.validator.Eval
+        self.valid_iterations = self.validator.valid_iterations
+
+    def build_validator(self, args):
         w, h = args.target_crop_size
         images = getattr(args, "val_images", 0) or args.synthetic_images
         # evaluate.py:64-79: with --data_root_path the val split of --dataset from files (batch size 1)
@@ -65,11 +75,10 @@ class Evaluater:
         if getattr(args, "data_root_path", None) is not None:
             self.dataloader = build_loader(args.dataset, args, False, dataset_paths(
                 args.dataset, args.data_root_path, args.list_path, getattr(args, "gt_path", None)))
-        self.validator = Validator(self.model, args.num_classes, (h, w), images, self.device,
-                                   flip=bool(getattr(args, "flip", False)), graph=bool(getattr(args, "graph", False)),
-                                   data=self.dataloader.val_loader if self.dataloader else None)
-        self.Eval = self.validator.Eval
-        self.valid_iterations = self.validator.valid_iterations
+        return Validator(self.model, args.num_classes, (h, w), images, self.device,
+                         flip=bool(getattr(args, "flip", False)), graph=bool(getattr(args, "graph", False)),
+                         data=self.dataloader.val_loader if self.dataloader else None,
+                         outputs=output_request(args))
 
     def main(self):
         self.logger.info("This model will run on %s", torch.cuda.get_device_name(self.device))
@@ -98,12 +107,39 @@ class Evaluater:
             self.args.crop_size = ckpt["crop_size"]
 
 
+def output_request(args, out_size=None):
+    """The OutputRequest of --save_predictions / --save_kinds / --threshold / --image_summary; None
+    without either flag (today's runs)."""
+    directory, every = getattr(args, "save_predictions", None), None
+    if directory is None and getattr(args, "image_summary", False):
+        directory, every = os.path.join(str(args.save_dir), "images"), SUMMARY_EVERY
+    if directory is None:
+        return None
+    return OutputRequest(directory, getattr(args, "save_kinds", ("color",)), getattr(args, "threshold", 0.95),
+                         getattr(args, "data_loader_workers", 0), out_size=out_size, every=every)
+
+
+def add_save_args(parser):
+    a = parser.add_argument
+    a("--save_predictions", type=str, default=None, metavar="DIR",
+      help="write every item's prediction as PNGs under DIR, one sub-directory per kind (not in the reference)")
+    a("--save_kinds", type=parse_save_kinds, default=("color",),
+      help="comma-separated: color,trainids,labelids,confidence,pseudo,input (default color)")
+    if not any("--threshold" in act.option_strings for act in parser._actions):
+        a("--threshold", type=float, default=0.95, help="the pseudo kind keeps a class where its probability > this")
+    return parser
+
+
 def build_parser():
     parser = add_train_args(argparse.ArgumentParser())  # --val_images is one of the train flags
     parser.add_argument("--flip", type=str2bool, default=False,
                         help="average the softmax of the image and of its horizontal mirror (evaluate.py:120-135)")
     parser.add_argument("--graph", type=str2bool, default=False,
                         help="replay each image after the first as one captured hipGraph (not in the reference)")
+    add_save_args(parser)
+    parser.add_argument("--image_summary", type=str2bool, default=False,
+                        help="the reference's image summaries as files: --save_predictions <save_dir>/images for "
+                             "every 20th item and the last")
     return parser
 
 

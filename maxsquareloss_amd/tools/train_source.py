@@ -37,6 +37,7 @@ from ..utils.loss import CrossEntropyLoss
 from ..utils.optim import SGD, Adam
 from ..utils.synthetic import SyntheticDomain, init_weights
 from ..utils.train_helper import get_model
+from ..utils.images import OutputRequest
 from ..utils.validate import Validator, val_info
 
 ITER_MAX = 5000
@@ -180,8 +181,13 @@ class Trainer:
         (utils/validate.py); returns (PA, MPA, MIoU, FWIoU), the 13-class numbers for 16 classes."""
         if self._validator is None:
             w, h = self.args.target_crop_size
+            outputs = None
+            if getattr(self.args, "val_save_predictions", None):  # the reference's image summaries, as files
+                outputs = OutputRequest(self.args.val_save_predictions, ("color",),
+                                        workers=getattr(self.args, "data_loader_workers", 0),
+                                        first=self.args.show_num_images)
             self._validator = Validator(self.model, self.args.num_classes, (h, w), self.args.val_images,
-                                        self.device, rank=self.rank, data=self.val_data())
+                                        self.device, rank=self.rank, data=self.val_data(), outputs=outputs)
         self.logger.info("validating one epoch...")
         ev = self._validator.run()
         out = val_info(ev, self.logger, self.current_epoch if epoch is None else epoch)
@@ -341,6 +347,9 @@ def add_train_args(arg_parser):
     a("--val_images", type=int, default=0,
       help="synthetic val items: with N > 0 the trainers validate after every epoch (best_MIou, "
            "<train_id>best.pth), tools/evaluate.py evaluates N items; 0 = no validation while training")
+    a("--val_save_predictions", type=str, default=None, metavar="DIR",
+      help="at every validation write the coloured prediction of the first --show_num_images val items as "
+           "DIR/color/NAME.png (the reference's image summaries, as files); default off")
     a("--conv_math", default="fp32", choices=["fp32", "fp16", "bf16"],
       help="conv MFMA precision (not in the reference, which is fp32): fp16 = BASELINE config 5's "
            "fp16 MFMA path (scaled fp16 operands, fp32 sums), bf16 = bf16 products, fp32 sums; BN, "

@@ -60,12 +60,14 @@ class Eval:
                                                    self._dev.data_ptr(), None, hip.stream_ptr()),
                       "msl_confusion_accumulate")
 
-    def add_batch_low(self, gt_image, low, out_hw, low_flip=None):
+    def add_batch_low(self, gt_image, low, out_hw, low_flip=None, images=None, thr=0.95):
         """add_batch from the LOW-resolution logits `low` (1,C,hi,wi) of one image: the class of every
         pixel of out_hw and its matrix cell in one kernel (ops.predict_up), the upsampled prediction
         never written.  With `low_flip` (the mirrored image's low-res logits) the class is the
         evaluator's --flip average (tools/evaluate.py:120-135); without, add_batch's argmax of
-        ops.upsample_bilinear(low, out_hw), bit for bit."""
+        ops.upsample_bilinear(low, out_hw), bit for bit.  `images` (a dict of uint8 buffers,
+        ops.image_buffers) also receives that class as images, still in the one launch
+        (ops.predict_images; `thr` is the pseudo-label threshold)."""
         if not (torch.is_tensor(low) and low.is_cuda and low.dim() == 4 and low.size(0) == 1):
             raise hip.MSLError("Eval.add_batch_low: expects device logits [1, C, hi, wi]")
         c = low.size(1)
@@ -76,7 +78,10 @@ class Eval:
             raise hip.MSLError("Eval.add_batch_low: label and prediction sizes differ")
         if self._dev is None or self._dev.device != low.device:
             self._dev = torch.zeros(c * c, dtype=torch.int64, device=low.device)
-        ops.predict_up(low, out_hw, low_flip, gt, self._dev)
+        if images is not None:
+            ops.predict_images(low, out_hw, low_flip, gt, self._dev, out=images, thr=thr)
+        else:
+            ops.predict_up(low, out_hw, low_flip, gt, self._dev)
 
     def reset(self):
         self._host = np.zeros((self.num_class,) * 2)
