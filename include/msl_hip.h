@@ -671,6 +671,28 @@ int msl_resize_nearest_label(const uint8_t* ids, int sh, int sw, int x0, int y0,
                              uint8_t* out_u8, int64_t* out_i64, msl_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * PNG unfilter of one byte lane (SYNTHIA's 16-bit label PNGs, synthia_Dataset.py:88-90: the reference
+ * keeps the low byte of R; the host inflates, the device undoes the scanline filters).
+ * scan: DEVICE inflated scanlines, row r at scan + r * row_stride = its filter byte, then w * bpp filtered
+ * bytes.  out: DEVICE (h, w) uint8 = byte `lane` of every reconstructed pixel, per the PNG specification:
+ * None, Sub, Up as written there, Average = floor((a + b) / 2) on the 9-bit sum, Paeth with ties broken
+ * in the order a, b, c; all mod 256; neighbours outside the image are 0.  PNG filters byte i from bytes
+ * i - bpp of the same row and i, i - bpp of the row above - the same lane of the neighbouring pixels -
+ * so one lane needs only itself (with the compacted plane of utils/png.py lane_plane: bpp = 1, lane = 0,
+ * row_stride = 1 + w).
+ * One launch of one workgroup, stream-ordered, no host synchronisation; every loop count and barrier
+ * of the kernel is a function of (h, w) alone.  msl_png_unfilter_band_rows() = the rows one pass of the
+ * kernel holds (taller images run as successive bands; for the tests).
+ * A filter byte above 4 cannot be seen from the host side of this call: the kernel treats such a row as
+ * None (filter 0) and reads nothing out of range (utils/png.py refuses such a file before any upload).
+ * MSL_ERR_ARG, before any launch: a NULL pointer, h or w < 1 or over 65535, bpp outside 1..8,
+ * lane >= bpp (or negative), row_stride < 1 + w * bpp.
+ * ---------------------------------------------------------------------- */
+int msl_png_unfilter_lane(const uint8_t* scan, int h, int w, int bpp, int lane, size_t row_stride, uint8_t* out,
+                          msl_stream_t stream);
+int msl_png_unfilter_band_rows(void);
+
+/* ------------------------------------------------------------------------
  * SGD step with the reference's duplicated-parameter semantics (quirk Q2):
  * torch.optim.SGD(momentum, weight_decay) single-tensor loop over the
  * optim_parameters() groups (train_source.py:139-144, deeplab_multi.py:132-171),

@@ -1,14 +1,17 @@
 """File-backed datasets with the reference's names (datasets/cityscapes_Dataset.py,
-datasets/gta5_Dataset.py): PNGs decoded by Pillow on the host, everything after the decode -
-mirror, crop, BICUBIC / NEAREST resize, BGR - mean, id -> trainId - on the device, byte-exact
-(utils/preprocess.py resize_image / resize_label)."""
+datasets/gta5_Dataset.py, datasets/synthia_Dataset.py): PNGs decoded on the host - by Pillow, SYNTHIA's
+16-bit labels by utils/png.py up to the inflate - everything after the decode - the PNG unfilter of those
+labels, mirror, crop, BICUBIC / NEAREST resize, BGR - mean, id -> trainId - on the device, byte-exact
+(utils/preprocess.py png_unfilter / resize_image / resize_label)."""
 from .cityscapes_Dataset import City_DataLoader, City_Dataset, Client_dataset, DeviceLoader  # noqa: F401
 from .gta5_Dataset import GTA5_DataLoader, GTA5_Dataset  # noqa: F401
+from .synthia_Dataset import SYNTHIA_DataLoader, SYNTHIA_Dataset  # noqa: F401
 
 
 def build_loader(name, args, training, paths):
-    """The loader of dataset `name` ('cityscapes' | 'gta5') over paths = {data_root_path, list_path,
-    gt_path}; SYNTHIA's 16-bit label PNGs need imageio's FreeImage plugin and stay out."""
+    """The loader of dataset `name` ('cityscapes' | 'gta5' | 'synthia') over paths = {data_root_path,
+    list_path, gt_path}.  SYNTHIA's tree is checked before anything else, so a wrong root is reported as
+    such whatever else is missing."""
     from ..hip import MSLError
     key = str(name).lower()
     if key == "cityscapes":
@@ -16,7 +19,7 @@ def build_loader(name, args, training, paths):
     if key == "gta5":
         return GTA5_DataLoader(args, training=training, datasets_path=paths)
     if key == "synthia":
-        raise MSLError("file-backed SYNTHIA is not supported: its 16-bit label PNGs need imageio's FreeImage "
-                       "plugin, which this package does not depend on; use --source_dataset gta5, or leave the "
-                       "data paths unset for the synthetic loaders")
-    raise MSLError(f"no file-backed loader for dataset {name!r} (cityscapes | gta5)")
+        from .synthia_Dataset import check_tree
+        check_tree(paths)
+        return SYNTHIA_DataLoader(args, training=training, datasets_path=paths)
+    raise MSLError(f"no file-backed loader for dataset {name!r} (cityscapes | gta5 | synthia)")

@@ -115,6 +115,8 @@ SIGNATURES = {
     "msl_resize_bicubic_rgb": (c_int, [c_p] + [c_int] * 7 + [c_p, c_p, c_int, c_p, c_p, c_int, c_int, c_int, c_p, c_p,
                                        c_f, c_f, c_f, c_p, c_sz, c_p]),
     "msl_resize_nearest_label": (c_int, [c_p] + [c_int] * 7 + [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
+    "msl_png_unfilter_lane": (c_int, [c_p, c_int, c_int, c_int, c_int, c_sz, c_p, c_p]),
+    "msl_png_unfilter_band_rows": (c_int, []),
     "msl_im2col": (c_int, [c_p] + [c_int] * 11 + [c_p, c_p]),
     "msl_col2im": (c_int, [c_p] + [c_int] * 11 + [c_p, c_p]),
     "msl_maxpool_fwd": (c_int, [c_p] + [c_int] * 8 + [c_p, c_p, c_p]),

@@ -72,9 +72,11 @@ def _free_port():
 def dataset_paths(dataset, data_root_path, list_path, gt_path=None):
     """The {data_root_path, list_path, gt_path} of one file-backed dataset.  Without a gt path the
     reference's layout (train_source.py:27-60): Cityscapes <root>/gtFine beside the images'
-    <root>/leftImg8bit..., GTA5 <root>/labels; the list path defaults to the data root."""
+    <root>/leftImg8bit..., GTA5 <root>/labels, SYNTHIA <root>/GT/LABELS (synthia_Dataset.py:51); the list
+    path defaults to the data root."""
     if gt_path is None:
-        gt_path = os.path.join(data_root_path, "labels" if str(dataset).lower() == "gta5" else "gtFine")
+        sub = {"gta5": "labels", "synthia": os.path.join("GT", "LABELS")}.get(str(dataset).lower(), "gtFine")
+        gt_path = os.path.join(data_root_path, sub)
     return {"data_root_path": data_root_path, "list_path": list_path or data_root_path, "gt_path": gt_path}
 
 

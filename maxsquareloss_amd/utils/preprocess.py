@@ -13,6 +13,9 @@ resize_image / resize_label run what comes before that in the reference's _train
 _val_sync_transform (:173-243) - Image.transpose, crop, resize with BICUBIC / NEAREST - byte-exact
 against Pillow on the device (csrc/resample.hip, tables from utils/resample.py), ending in the same
 two transforms.
+
+png_unfilter undoes the PNG scanline filters of one byte lane on the device (csrc/png.hip): SYNTHIA's
+16-bit label PNGs are inflated on the host (utils/png.py) and reconstructed here, ahead of resize_label.
 """
 import numpy as np
 import torch
@@ -187,4 +190,26 @@ def resize_label(ids, out_wh, lut, crop=None, mirror=False):
     hip.check(hip.load().msl_resize_nearest_label(
         ids.data_ptr(), h, w, x1, y1, cw, ch, int(bool(mirror)), hip.ptr(xtab), hip.ptr(ytab), ow, oh,
         hip.ptr(dlut), out_u8, out_i64, hip.stream_ptr()), "msl_resize_nearest_label")
+    return out
+
+
+# ---------------------------------------------------------------------------- PNG unfilter (SYNTHIA labels)
+def png_unfilter(plane_or_scan, bpp=1, lane=0):
+    """Inflated PNG scanlines -> byte `lane` of every reconstructed pixel (csrc/png.hip, one launch on the
+    current stream).  plane_or_scan: CUDA uint8 (h, 1 + w * bpp), each row its filter byte and the filtered
+    bytes (utils/png.py read_scanlines; with the defaults the compacted plane of lane_plane).  Returns CUDA
+    uint8 (h, w), what utils/png.py unfilter_lane gives on the host."""
+    t = plane_or_scan
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 2:
+        raise hip.MSLError("png_unfilter: expected a CUDA uint8 (h, 1 + w * bpp) tensor of scanlines")
+    bpp, lane = int(bpp), int(lane)
+    if bpp < 1 or t.size(1) < 1 + bpp or (t.size(1) - 1) % bpp:
+        raise hip.MSLError(f"png_unfilter: rows of {t.size(1)} bytes are not a filter byte and whole pixels of "
+                           f"{bpp} bytes")
+    if t.stride(1) != 1:
+        t = t.contiguous()
+    h, w = t.size(0), (t.size(1) - 1) // bpp
+    out = torch.empty((h, w), dtype=torch.uint8, device=t.device)
+    hip.check(hip.load().msl_png_unfilter_lane(t.data_ptr(), h, w, bpp, lane, t.stride(0), out.data_ptr(),
+                                               hip.stream_ptr()), "msl_png_unfilter_lane")
     return out
