@@ -768,6 +768,65 @@ int msl_adam_step_lr_dev(const msl_adam_entry* entries, int n_entries, const int
                          double beta1, double beta2, double eps, float weight_decay, float grad_scale,
                          float* coef, msl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * AdaIN style pass (the reference's utils/style_transform.py over tools/net.py), everything but its 3x3
+ * convs, which are msl_dconv_fwd.  One image per call, [C][H][W] fp32.
+ *
+ * The reference pads every conv by reflection; msl_dconv_fwd pads with zeros.  A stage's input is
+ * therefore written WITH its reflected border as a padded grid [C][H+2][W+2], the conv runs over the
+ * whole grid (dilation 1), and only the interior [1..H] x [1..W] of its output is read afterwards: interior
+ * outputs touch the grid's own cells only, border outputs are finite and ignored.  An input `x` with
+ * x_grid = 1 is such a grid, read through its interior; with x_grid = 0 a plain [C][H][W] tensor.
+ * Every entry point checks its arguments before any launch: a NULL pointer, a size <= 0, a flag out of
+ * range or a tensor of 2^31 or more cells is MSL_ERR_ARG, a shape the operation is undefined on
+ * MSL_ERR_SHAPE.
+ * ---------------------------------------------------------------------- */
+/* y[cpad][ho+2][wo+2] = reflect_pad1(resample(f(x))), one launch.
+ *   resample  0 none (ho = h), 1 the 2x2 stride-2 ceil-mode max-pool (ho = ceil(h/2); the last window of
+ *             an odd axis holds one row / column), 2 nearest x2 (ho = 2h); wo likewise
+ *   a, b      both NULL, or DEVICE arrays of c floats: the per-channel affine a_c * v + b_c (the multiply
+ *             and the add rounded separately); without them the kernel does no arithmetic
+ *   act       0: f(v) = a v + b;  1: f(v) = relu(a v + b);  2: f(v) = a relu(v) + b (the AdaIN affine
+ *             over the encoder's last ReLU)
+ *   cpad      >= c channels of y; the ones past c are zero (a caller pads a conv's cin with them)
+ * Without the affine every cell is a copy or a max of inputs, bit-identical to torch's ReLU,
+ * MaxPool2d((2,2),(2,2),(0,0),ceil_mode=True), Upsample(scale_factor=2, mode='nearest') and
+ * ReflectionPad2d(1) (ReLU keeps -0.0; of equal window values the first in row-major order stays).
+ * MSL_ERR_SHAPE: h < 2 or w < 2, or ho < 2 or wo < 2 (reflection needs two rows and two columns). */
+int msl_style_pad(const float* x, int x_grid, int c, int h, int w, int act, int resample, const float* a,
+                  const float* b, float* y, int cpad, msl_stream_t stream);
+/* y[cpad][h+2][w+2] = reflect_pad1(W1 v + b1): the encoder's leading 1x1 conv 3 -> 3 (w1: DEVICE [3][3],
+ * b1: DEVICE [3]) as a per-pixel affine, the channels past 3 zero.  v is exactly one of rgb_u8 (uint8
+ * [h][w][3] RGB, divided by 255 as torchvision's ToTensor does) and chw_f32 (float [3][h][w] in [0, 1]).
+ * MSL_ERR_SHAPE: h < 2 or w < 2. */
+int msl_style_input(const uint8_t* rgb_u8, const float* chw_f32, int h, int w, const float* w1, const float* b1,
+                    float* y, int cpad, msl_stream_t stream);
+/* stats[0..c) = the mean and stats[c..2c) = the unbiased variance of each channel over its h*w pixels,
+ * of relu(x) when `relu`.  Values are reduced as differences from the channel's first pixel (a large mean
+ * with a small spread keeps its variance), in batches of 8 by the corrected two-pass sum in registers, merged
+ * by Chan's update through wave shuffles and LDS; channels of more than 8192 pixels take a second launch over
+ * the blocks' moments in `ws` (msl_style_stats_workspace bytes, 0 for smaller channels; MSL_ERR_WORKSPACE if
+ * short).  No atomics: the same input gives the same bits.  MSL_ERR_SHAPE: h*w < 2. */
+size_t msl_style_stats_workspace(int c, int h, int w);
+int msl_style_stats(const float* x, int x_grid, int c, int h, int w, int relu, float* stats, void* ws,
+                    size_t ws_bytes, msl_stream_t stream);
+/* The AdaIN affine of a content map toward nstyle weighted styles, one launch, no host sync:
+ *   a_c = alpha * (sum_i w_i ss_i) / sc + (1 - alpha),  b_c = alpha * (sum_i w_i ms_i - mc * (sum_i w_i ss_i) / sc)
+ * with m the mean and s = sqrt(var + eps) of content_stats [2][c] and style_stats [nstyle][2][c] (DEVICE,
+ * as msl_style_stats writes them); `weights` is a HOST array of nstyle floats (the reference's
+ * interpolation_weights; {1} for one style), 1 <= nstyle <= msl_style_max_styles() (16).  alpha = 0 gives
+ * a = 1, b = 0 exactly.  MSL_ERR_ARG: alpha outside [0, 1], eps < 0. */
+int msl_style_max_styles(void);
+int msl_style_adain_coef(const float* content_stats, const float* style_stats, const float* weights, int nstyle,
+                         int c, float alpha, float eps, float* a, float* b, msl_stream_t stream);
+/* From a 3-channel RGB map x (the decoder's output), q = clamp(x * 255 + 0.5, 0, 255) rounded as torch's
+ * mul(255).add(0.5).clamp(0, 255), into either or both of
+ *   rgb_u8   uint8 [h][w][3] RGB = uint8(q): torchvision save_image's quantisation
+ *   seg_bgr  float [3][h][w] = q of B, G, R minus mean_b, mean_g, mean_r, not truncated: the reference's
+ *            Trainer.seg_transform, the segmentation network's input */
+int msl_style_output(const float* x, int x_grid, int h, int w, uint8_t* rgb_u8, float* seg_bgr, float mean_b,
+                     float mean_g, float mean_r, msl_stream_t stream);
+
 /* Diagnostics (r06): the launch guard every entry point runs before each kernel launch (MSL_ERR_LAUNCH
  * when a block exceeds the kernel's __launch_bounds__).  Launches a 256-thread-bound probe kernel with
  * `threads` threads writing out[t] = t: MSL_OK (and out[0 .. threads) written) for 1 <= threads <= 256,

@@ -135,6 +135,13 @@ SIGNATURES = {
     "msl_adam_coef_bytes": (c_sz, [c_int]),
     "msl_adam_step": (c_int, [c_p, c_int, c_p, c_p, c_ll, c_f, c_f, c_d, c_d, c_d, c_f, c_f, c_p, c_p]),
     "msl_adam_step_lr_dev": (c_int, [c_p, c_int, c_p, c_p, c_ll, c_p, c_d, c_d, c_d, c_f, c_f, c_p, c_p]),
+    "msl_style_pad": (c_int, [c_p] + [c_int] * 6 + [c_p, c_p, c_p, c_int, c_p]),
+    "msl_style_input": (c_int, [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_int, c_p]),
+    "msl_style_stats_workspace": (c_sz, [c_int] * 3),
+    "msl_style_stats": (c_int, [c_p] + [c_int] * 5 + [c_p, c_p, c_sz, c_p]),
+    "msl_style_max_styles": (c_int, []),
+    "msl_style_adain_coef": (c_int, [c_p, c_p, c_p, c_int, c_int, c_f, c_f, c_p, c_p, c_p]),
+    "msl_style_output": (c_int, [c_p] + [c_int] * 3 + [c_p, c_p, c_f, c_f, c_f, c_p]),
     "msl_launch_guard_probe": (c_int, [c_int, c_p, c_p]),
     "msl_pconv_dgrad_resmask_sc": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_p, c_p, c_sz, c_p, c_p,
                                            c_int]),

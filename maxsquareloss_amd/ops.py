@@ -1642,3 +1642,129 @@ def bn_act(bn, x, residual=None, relu=False, residual_grad=None):
     return _BNAct.apply(x, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
                         bn.num_batches_tracked if training else None, training, momentum, bn.eps, relu,
                         residual_grad)
+
+
+# --------------------------------------------------------------------------- AdaIN style pass (csrc/style.hip)
+# Forward only, no autograd: the style network runs under no_grad in the reference too
+# (utils/style_transform.py).  A "grid" is a stage's input with its reflected border, (1, C, H+2, W+2);
+# the kernels read a grid's interior or a plain (1, C, H, W) tensor (include/msl_hip.h).
+STYLE_ACT = {"none": 0, "relu": 1, "relu_in": 2}
+STYLE_RESAMPLE = {"none": 0, "pool": 1, "up": 2}
+
+
+def _style_src(x, grid, name):
+    """(contiguous x, C, H, W) of a plain (1,C,H,W) tensor or, with `grid`, of a grid's interior."""
+    if not (x.is_cuda and x.dtype == _f32 and x.dim() == 4 and x.size(0) == 1):
+        raise hip.MSLError(f"{name}: expected a CUDA fp32 tensor of shape (1,C,H,W), got {tuple(x.shape)} {x.dtype} "
+                           f"{x.device}")
+    pad = 2 if grid else 0
+    return x.contiguous(), x.size(1), x.size(2) - pad, x.size(3) - pad
+
+
+def style_out_hw(h, w, resample):
+    """The interior size of style_pad's output grid."""
+    if resample == "pool":
+        return (h + 1) // 2, (w + 1) // 2
+    return (2 * h, 2 * w) if resample == "up" else (h, w)
+
+
+def style_pad(x, grid=False, act="none", resample="none", a=None, b=None, cpad=None):
+    """reflect_pad1(resample(f(x))) as a grid (1, cpad, H'+2, W'+2): msl_style_pad, one launch.  act "relu"
+    applies after the per-channel affine a, b (device tensors of C floats, or both None), "relu_in" before."""
+    x, c, h, w = _style_src(x, grid, "style_pad")
+    cpad = c if cpad is None else int(cpad)
+    ho, wo = style_out_hw(h, w, resample)
+    y = torch.empty((1, cpad, ho + 2, wo + 2), dtype=_f32, device=x.device)
+    if a is not None:
+        a, b = a.contiguous(), b.contiguous()
+        if a.numel() != c or b.numel() != c or a.dtype != _f32 or b.dtype != _f32:
+            raise hip.MSLError(f"style_pad: the affine needs two fp32 tensors of {c} elements")
+    hip.check(hip.load().msl_style_pad(x.data_ptr(), int(bool(grid)), c, h, w, STYLE_ACT[act], STYLE_RESAMPLE[resample],
+                                       hip.ptr(a), hip.ptr(b), y.data_ptr(), cpad, hip.stream_ptr()), "msl_style_pad")
+    return y
+
+
+def style_input(img, w1, b1, cpad=3):
+    """The encoder's first grid (1, cpad, H+2, W+2) from a uint8 (H, W, 3) RGB image (divided by 255) or a
+    float (1, 3, H, W) tensor in [0, 1], through the leading 1x1 conv (w1 (3,3,1,1), b1 (3,)): msl_style_input."""
+    if img.dtype == torch.uint8:
+        ok, h, w = img.dim() == 3 and img.size(2) == 3, img.size(0), img.size(1)
+    else:
+        ok, h, w = img.dtype == _f32 and img.dim() == 4 and tuple(img.shape[:2]) == (1, 3), img.size(-2), img.size(-1)
+    if not (ok and img.is_cuda):
+        raise hip.MSLError(f"style_input: expected a CUDA uint8 (H,W,3) or fp32 (1,3,H,W) image, got "
+                           f"{tuple(img.shape)} {img.dtype} {img.device}")
+    img, w1, b1 = img.contiguous(), w1.contiguous(), b1.contiguous()
+    if w1.numel() != 9 or b1.numel() != 3 or w1.dtype != _f32 or b1.dtype != _f32:
+        raise hip.MSLError("style_input: the 1x1 conv needs a (3,3,1,1) weight and a (3,) bias in fp32")
+    y = torch.empty((1, cpad, h + 2, w + 2), dtype=_f32, device=img.device)
+    u8 = img.dtype == torch.uint8
+    hip.check(hip.load().msl_style_input(img.data_ptr() if u8 else None, None if u8 else img.data_ptr(), h, w,
+                                         w1.data_ptr(), b1.data_ptr(), y.data_ptr(), cpad, hip.stream_ptr()),
+              "msl_style_input")
+    return y
+
+
+def style_stats(x, grid=False, relu=True):
+    """(2, C): the per-channel mean and unbiased variance of x (of relu(x) with `relu`): msl_style_stats."""
+    x, c, h, w = _style_src(x, grid, "style_stats")
+    lib = hip.load()
+    stats = torch.empty((2, c), dtype=_f32, device=x.device)
+    wsb = lib.msl_style_stats_workspace(c, h, w)
+    ws = hip.workspace(wsb, x.device)
+    hip.check(lib.msl_style_stats(x.data_ptr(), int(bool(grid)), c, h, w, int(bool(relu)), stats.data_ptr(),
+                                  ws.data_ptr(), wsb, hip.stream_ptr()), "msl_style_stats")
+    return stats
+
+
+def style_adain_coef(content_stats, style_stats_, weights=(1.0,), alpha=1.0, eps=1e-5):
+    """The AdaIN affine (a, b) of C floats each, from content statistics (2, C) and S style statistics
+    (S, 2, C) weighted by `weights`: msl_style_adain_coef, no host sync."""
+    c = content_stats.size(-1)
+    s = len(weights)
+    if tuple(content_stats.shape) != (2, c) or tuple(style_stats_.shape) != (s, 2, c):
+        raise hip.MSLError(f"style_adain_coef: statistics {tuple(content_stats.shape)} / {tuple(style_stats_.shape)} "
+                           f"do not match {s} weights")
+    content_stats, style_stats_ = content_stats.contiguous(), style_stats_.contiguous()
+    wt = (ctypes.c_float * s)(*[float(v) for v in weights])
+    ab = torch.empty((2, c), dtype=_f32, device=content_stats.device)
+    hip.check(hip.load().msl_style_adain_coef(content_stats.data_ptr(), style_stats_.data_ptr(),
+                                              ctypes.addressof(wt), s, c, float(alpha), float(eps), ab[0].data_ptr(),
+                                              ab[1].data_ptr(), hip.stream_ptr()), "msl_style_adain_coef")
+    return ab[0], ab[1]
+
+
+def style_output(x, grid=False, rgb=True, seg=False, mean=(0.0, 0.0, 0.0)):
+    """(uint8 (H, W, 3) RGB or None, fp32 (1, 3, H, W) BGR - mean or None) of a 3-channel map in [0, 1]:
+    msl_style_output; `mean` in B, G, R order."""
+    x, c, h, w = _style_src(x, grid, "style_output")
+    if c != 3 or not (rgb or seg):
+        raise hip.MSLError(f"style_output: expected 3 channels and at least one output, got {c} channels")
+    u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=x.device) if rgb else None
+    sg = torch.empty((1, 3, h, w), dtype=_f32, device=x.device) if seg else None
+    hip.check(hip.load().msl_style_output(x.data_ptr(), int(bool(grid)), h, w, hip.ptr(u8), hip.ptr(sg), float(mean[0]),
+                                          float(mean[1]), float(mean[2]), hip.stream_ptr()), "msl_style_output")
+    return u8, sg
+
+
+def conv3x3_reflect(x_grid, weight, bias, cache):
+    """The reference's ReflectionPad2d(1) + Conv2d(cin, cout, 3) on a grid (1, cin, H+2, W+2) that already
+    holds the reflected border: msl_dconv_fwd (one branch, dilation 1, zero padding) over the whole grid.
+    Returns (1, cout, H+2, W+2), of which only the interior is the conv's output (the border cells also
+    read the zero padding: finite, never to be read).  Forward only."""
+    x, cin, h, w = _style_src(x_grid, False, "conv3x3_reflect")
+    cout = weight.size(0)
+    if tuple(weight.shape) != (cout, cin, 3, 3) or (bias is not None and bias.numel() != cout):
+        raise hip.MSLError(f"conv3x3_reflect: weight {tuple(weight.shape)} does not match input {tuple(x.shape)}")
+    lib = hip.load()
+    packed = cache.get([weight], cin, cout, 0)
+    y = torch.empty((1, cout, h, w), dtype=_f32, device=x.device)
+    wsb = lib.msl_dconv_fwd_workspace(1, cin, cout, h, w, 1)
+    ws = hip.workspace(wsb, x.device)
+    math = CONV_MATH
+    xpart = _parts(x, math, compute=_split_gemm(cout, cin))
+    hip.check(_conv_call(lib, "msl_dconv_fwd", math,
+                         (x.data_ptr(), packed.data_ptr(), hip.ptr(None if bias is None else bias.detach().contiguous()),
+                          y.data_ptr(), 1, cin, cout, h, w, 1, 1, 0, hip.forms(), ws.data_ptr(), wsb, hip.stream_ptr()),
+                         (xpart,)), "msl_dconv_fwd")
+    return y

@@ -87,6 +87,11 @@ def _encode(directory, name, arrays):
         Image.fromarray(arr).save(os.path.join(directory, kind, name + ".png"))
 
 
+def _encode_file(path, arr):
+    from PIL import Image
+    Image.fromarray(arr).save(path)
+
+
 class _Slot:
     def __init__(self):
         self.buf, self.future = {}, None
@@ -108,14 +113,16 @@ class _Slot:
 class ImageWriter:
     """save(name, {kind: uint8 map}) writes <directory>/<kind>/<name>.png for every kind given; device
     tensors are copied on the current stream.  `workers` host threads (at most 16) encode; each save uses
-    the next of max(2, workers + 1) host slots and first waits for the encode that last used it."""
+    the next of max(2, workers + 1) host slots and first waits for the encode that last used it.
+    save_as(relpath, map) writes one map to <directory>/<relpath> the same way (tools/stylize.py)."""
 
     def __init__(self, directory, kinds=SAVE_KINDS, workers=0):
         try:
             from PIL import Image  # noqa: F401
         except ImportError as e:
             raise MSLError("saving predictions encodes PNGs with Pillow, which is not installed") from e
-        self.directory, self.kinds = str(directory), parse_save_kinds(",".join(kinds))
+        # kinds () = no per-kind sub-directories: a writer of whole files (save_as) only
+        self.directory, self.kinds = str(directory), parse_save_kinds(",".join(kinds)) if kinds else ()
         for k in self.kinds:
             os.makedirs(os.path.join(self.directory, k), exist_ok=True)
         self.workers = max(0, min(int(workers), MAX_WRITER_THREADS))
@@ -128,6 +135,19 @@ class ImageWriter:
         bad = [k for k in maps if k not in self.kinds]
         if bad:
             raise MSLError(f"ImageWriter: kinds {bad} were not requested ({','.join(self.kinds)})")
+        name = str(name)
+        self._stage_and_encode(maps, lambda arrays: _encode(self.directory, name, arrays))
+        self.written.append(name)
+
+    def save_as(self, relpath, t):
+        """Write one uint8 map to <directory>/<relpath>, in the format of the path's extension (the
+        stylised datasets of tools/stylize: PNG or JPEG, any sub-directory)."""
+        path = os.path.join(self.directory, str(relpath))
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        self._stage_and_encode({"file": t}, lambda arrays: _encode_file(path, arrays["file"]))
+        self.written.append(str(relpath))
+
+    def _stage_and_encode(self, maps, encode):
         slot = self._slots[self._n % len(self._slots)]
         self._n += 1
         if slot.future is not None:
@@ -139,13 +159,11 @@ class ImageWriter:
         if on_device:
             event = torch.cuda.Event()
             event.record(torch.cuda.current_stream(on_device[0].device))
-        name = str(name)
-        self.written.append(name)
 
         def job():
             if event is not None:
                 event.synchronize()
-            _encode(self.directory, name, arrays)
+            encode(arrays)
 
         if self._pool is None:
             job()
