@@ -368,6 +368,43 @@ int msl_conv_fwd_plan(int family, int nbranch, int taps, int cimg, int M, int P,
                       const msl_forms* forms, msl_conv_fwd_plan_info* out);
 
 /* ------------------------------------------------------------------------
+ * The plan of a weight-gradient call (msl_dconv_wgrad* / msl_pconv_wgrad* of every family), as a
+ * host-only query: no launch, no pointers to data, usable without a GPU.  It reports what the call
+ * launches through the very functions the launch calls (the operand swap, the GEMM kernel and the
+ * math it was instantiated with, the piece reduce, the refusal, the scale mode), so it cannot drift
+ * from it.  The tests hold every reachable (GEMM, reduce, orientation, taps) and schedule class to fp64
+ * through it (tests/conv_wgrad_cases.py).  Additive: ABI 3.  Replaces nothing in the reference.
+ * ---------------------------------------------------------------------- */
+typedef struct msl_conv_wgrad_plan_info {
+  int gemm;      /* 0 k_wgrad_sk (64-pixel K-steps), 1 k_wgrad_x6 (16-pixel K-steps on a pre-split operand) */
+  int bm, bn;    /* its tile */
+  int math;      /* the math it was instantiated with (msl_conv_form.math: 0, 1, 2, 5, 8) - the math
+                    launched, not the family's: the fp16 family runs 2 on k_wgrad_sk's 128-row tile and
+                    0 on its 64- and 32-row tiles */
+  int split_rows; /* k_split_rows runs first (gemm 1) */
+  int reduce;    /* the piece reduce: 0 k_wsk_reduce<32,128>, 1 k_wsk_reduce<64,64>, 2 k_wsk_reduce_wide<64,64,8>,
+                    3 k_wsk_reduce<128,128>, 4 k_wsk_reduce_split<128,128,4> */
+  int trans;     /* operands swapped (M = cin, N = cout), the dW^T tiles written transposed */
+  int tiles_m, tiles_n, ntap; /* tiles of the (swapped) M and N, nbranch * taps */
+  int KS, bk;    /* K-steps of one tile, pixels per K-step */
+  int NW, T, slots; /* workgroups, (tile, K-step) items, pieces a worker can leave */
+  int nchunk, kchunk; /* chunked split-K (gemm 1): chunks per tile and K-steps per chunk; 0 0 = stream-K ranges */
+  int swizzle;   /* the XCD worker swizzle is on (NW a multiple of 8) */
+  int max_run;   /* the longest run of K-steps one worker gives to one tile */
+  int mask_tab;  /* gemm 1: that run reads its border masks from the LDS table (1) or takes the scalar
+                    cursor (0); 0 for gemm 0 */
+  int rowscale;  /* fp16 planes (math 5, 8 on gemm 1): 1 one scale per row, 0 one per tensor */
+  int status;    /* what the call returns given a sufficient workspace: MSL_OK or MSL_ERR_SHAPE */
+} msl_conv_wgrad_plan_info;
+/* family as msl_conv_fwd_plan.  taps 9: msl_dconv_wgrad* on nimg images of h x w (nbranch 1 or 2);
+ * taps 1: msl_pconv_wgrad* with p = nimg*h*w (nbranch 1, has_dbias 0), planned on one flat row as the
+ * call plans it.  x_npart / dy_npart: the partial counts the caller passes with x / dy (0 = none: the call
+ * reduces one per row itself).  MSL_ERR_ARG on anything else, incl. forms the family cannot run. */
+int msl_conv_wgrad_plan(int family, int nbranch, int taps, int cin, int cout, int h, int w, int nimg,
+                        int has_dbias, int x_npart, int dy_npart, const msl_forms* forms,
+                        msl_conv_wgrad_plan_info* out);
+
+/* ------------------------------------------------------------------------
  * Bilinear upsample, align_corners=True (F.interpolate at deeplab_multi.py:124,
  * :128).  The forward reproduces torch-CPU's rounding bit for bit.
  * ---------------------------------------------------------------------- */

@@ -863,33 +863,82 @@ static size_t wgrad_ws_bytes(int nbranch, int taps, int cin, int cout, int P, in
   return wgrad_core_bytes(nbranch, taps, cin, cout, P, w) + align_up((size_t)(cin + cout) * 4, 16) + 16;
 }
 
+// ---- the choices of a weight-gradient call, shared by the launch (launch_wgrad) and the query
+// (msl_conv_wgrad_plan): the math family's fp32-accurate split forms, the plan with its operand swap,
+// the math each GEMM kernel is instantiated with, the piece reduce, the refusal and the scale mode.
+constexpr bool wgrad_f16(int mt) { return mt == kMathH3P || mt == kMathH1P; }
+constexpr bool wgrad_x6l(int mt) { return mt == kMathX6 || wgrad_f16(mt); }
+// the math of the GEMM kernel a plan of math family `mt` launches: k_wgrad_x6 runs the family's split (fp16:
+// its planes), k_wgrad_sk has no f16 form (x6 on its 128-row tile), and the split forms run only on 128x128
+// tiles (plan_wgrad): exact f32 on the 64- and 32-row ones
+constexpr int wgrad_gemm_math(int mt, bool rx6, int bm) {
+  if (rx6) return wgrad_f16(mt) ? mt : kMathX6;
+  if (bm == 128) return wgrad_f16(mt) ? kMathX6 : mt;
+  return wgrad_x6l(mt) ? kMathF32 : mt;
+}
+
+// The plan of the call; trans: it runs with the operands swapped (the plan is then of (cout, cin))
+static WgradPlan plan_wgrad_call(int mt, int nbranch, int taps, int cin, int cout, int P, int w, bool has_dbias,
+                                 bool& trans) {
+  const bool x6l = wgrad_x6l(mt);
+  WgradPlan pl = plan_wgrad(nbranch, taps, cin, cout, P, x6l, w);
+  trans = false;
+  if (x6l && wgrad_swaps(nbranch, taps, cin, cout) && !has_dbias) {
+    WgradPlan ps = plan_wgrad(nbranch, taps, cout, cin, P, true, w);
+    if (ps.rx6) {  // dW^T = image . dY^T: M = cin (pre-split), N = cout
+      pl = ps;
+      trans = true;
+    }
+  }
+  return pl;
+}
+
+// cin / cout as the plan sees them (after a swap): 32-bit index arithmetic, float pixel-row division in the kernel
+static int wgrad_refusal(const WgradPlan& pl, int cin, int cout, int P) {
+  if (pl.T * pl.nw >= (1LL << 31) || (long long)pl.nw * pl.slots * pl.bm * pl.bn * 4 >= (1LL << 31) ||
+      (long long)std::max(cin, cout) * P >= (1LL << 29) || (long long)P + kWskBK >= (1LL << 22))
+    return MSL_ERR_SHAPE;
+  return MSL_OK;
+}
+
+enum WgradReduce { kWrSk32, kWrSk64, kWrWide64, kWrSk128, kWrSplit128 };
+static unsigned wgrad_rgrid_x(const WgradPlan& pl, int taps) { return (unsigned)cdiv((long long)pl.bm * pl.bn / 4 * taps, 256); }
+static unsigned wgrad_rgrid_y(const WgradPlan& pl, int nbranch) { return (unsigned)(pl.tiles_m * pl.tiles_n * nbranch); }
+static WgradReduce wgrad_reduce(const WgradPlan& pl, int nbranch, int taps) {
+  const long long ntiles = (long long)pl.tiles_m * pl.tiles_n * pl.ntap;
+  // r06, k_wgrad_x6: S waves per 64 outputs, each summing every S-th piece (k_wsk_reduce_split), where a tile has >= 16
+  // pieces (the 16- and 9-tile layer3 1x1 / layer2 3x3 gradients: 32-56 chunks; at 8 pieces, 512 -> 2048, it lost 4 us)
+  const long long x6_pieces = pl.nchunk > 0 ? pl.nchunk : cdiv((long long)pl.nw, ntiles);
+  // 64 x 64, few tiles with many pieces each (the 33k-px 1x1 gradients: 4 tiles x ~128 pieces): 8 threads per
+  // output float4 (k_wsk_reduce_wide) instead of one serial chain of every piece
+  const long long sk_pieces = cdiv((long long)pl.nw, std::max(1LL, pl.T / pl.KS));  // per (tile, tap)
+  if (pl.rx6 && kWskSplit > 1 && x6_pieces >= kWskSplitMinPieces) return kWrSplit128;
+  if (pl.bm == 128) return kWrSk128;
+  if (pl.bm == 64 && (long long)wgrad_rgrid_x(pl, taps) * wgrad_rgrid_y(pl, nbranch) < 256 && sk_pieces >= 16)
+    return kWrWide64;
+  return pl.bm == 64 ? kWrSk64 : kWrSk32;
+}
+
+// one scale per row when both operands come with one maximum per row (M, N as the plan sees them)
+static int wgrad_rowscale(int anpart, int M, int bnpart, int N) { return (anpart == M && bnpart == N) ? 1 : 0; }
+
 template <int MT>
 static int launch_wgrad(WgradCall c, void* ws, size_t ws_bytes, hipStream_t st) {
   const ConvGeom& g = c.g;
   const int P = g.nimg * g.h * g.w, taps = g.taps, nbranch = g.nbranch;
-  constexpr bool F16 = MT == kMathH3P || MT == kMathH1P;
-  constexpr bool X6L = MT == kMathX6 || F16;
-  constexpr int MS = X6L ? kMathF32 : MT;  // the split forms only on 128x128 tiles (plan_wgrad)
-  constexpr int MB = F16 ? kMathX6 : MT;   // k_wgrad_sk has no f16 form: x6 there
-  constexpr int MX = F16 ? MT : kMathX6;   // k_wgrad_x6's
+  constexpr bool F16 = wgrad_f16(MT);
+  constexpr int MX = wgrad_gemm_math(MT, true, 128);  // k_wgrad_x6's
   if (ws_bytes < wgrad_ws_bytes(nbranch, taps, c.cin, c.cout, P, g.w)) return MSL_ERR_WORKSPACE;
-  WgradPlan pl = plan_wgrad(nbranch, taps, c.cin, c.cout, P, X6L, g.w);
   bool trans = false;
-  if (X6L && wgrad_swaps(nbranch, taps, c.cin, c.cout) && !c.dbias) {
-    WgradPlan ps = plan_wgrad(nbranch, taps, c.cout, c.cin, P, true, g.w);
-    if (ps.rx6) {  // dW^T = image . dY^T: M = cin (pre-split), N = cout
-      pl = ps;
-      trans = true;
-      std::swap(c.x, c.dy);
-      std::swap(c.x_part, c.dy_part);
-      std::swap(c.x_npart, c.dy_npart);
-      std::swap(c.cin, c.cout);
-    }
+  const WgradPlan pl = plan_wgrad_call(MT, nbranch, taps, c.cin, c.cout, P, g.w, c.dbias != nullptr, trans);
+  if (trans) {
+    std::swap(c.x, c.dy);
+    std::swap(c.x_part, c.dy_part);
+    std::swap(c.x_npart, c.dy_npart);
+    std::swap(c.cin, c.cout);
   }
   const int cin = c.cin, cout = c.cout;
-  if (pl.T * pl.nw >= (1LL << 31) || (long long)pl.nw * pl.slots * pl.bm * pl.bn * 4 >= (1LL << 31) || (long long)std::max(cin, cout) * P >= (1LL << 29) ||
-      (long long)P + kWskBK >= (1LL << 22))
-    return MSL_ERR_SHAPE;  // 32-bit index arithmetic, float pixel-row division in the kernel
+  if (const int refused = wgrad_refusal(pl, cin, cout, P)) return refused;
   WskArgs a{};
   a.dy = c.dy;
   a.x = c.x;
@@ -919,7 +968,7 @@ static int launch_wgrad(WgradCall c, void* ws, size_t ws_bytes, hipStream_t st) 
   a.ntiles = pl.tiles_m * pl.tiles_n * pl.ntap;
   a.trans = trans ? 1 : 0;
   const dim3 grid(pl.nw), block(256);
-  const dim3 rgrid(cdiv((long long)pl.bm * pl.bn / 4 * taps, 256), pl.tiles_m * pl.tiles_n * nbranch), rblock(256);
+  const dim3 rgrid(wgrad_rgrid_x(pl, taps), wgrad_rgrid_y(pl, nbranch)), rblock(256);
   // the GEMM
   if (pl.rx6) {
     bf16x8* planes = reinterpret_cast<bf16x8*>((char*)ws + wgrad_piece_bytes(pl));
@@ -943,38 +992,33 @@ static int launch_wgrad(WgradCall c, void* ws, size_t ws_bytes, hipStream_t st) 
         a.bpart = r2;
         a.bnpart = cin;
       }
-      a.rowscale = (a.anpart == cout && a.bnpart == cin) ? 1 : 0;
+      a.rowscale = wgrad_rowscale(a.anpart, cout, a.bnpart, cin);
     }
     MSL_LAUNCH(k_split_rows<MX>, dim3(pl.lda / kSplitRowsR, cdiv(pl.KS, 16)), block, 0, st, c.dy, cout, P, pl.KS,
                pl.lda, planes, a.apart, a.anpart, a.rowscale);
     MSL_CHECK_LAUNCH();
     MSL_LAUNCH(k_wgrad_x6<MX>, grid, block, 0, st, a);
   } else if (pl.bm == 128) {
-    MSL_LAUNCH((k_wgrad_sk<128, 128, 2, 2, 2, MB>), grid, block, 0, st, a);
+    MSL_LAUNCH((k_wgrad_sk<128, 128, 2, 2, 2, wgrad_gemm_math(MT, false, 128)>), grid, block, 0, st, a);
   } else if (pl.bm == 64) {
-    MSL_LAUNCH((k_wgrad_sk<64, 64, 2, 2, 2, MS>), grid, block, 0, st, a);
+    MSL_LAUNCH((k_wgrad_sk<64, 64, 2, 2, 2, wgrad_gemm_math(MT, false, 64)>), grid, block, 0, st, a);
   } else {
-    MSL_LAUNCH((k_wgrad_sk<32, 128, 2, 1, 4, MS>), grid, block, 0, st, a);
+    MSL_LAUNCH((k_wgrad_sk<32, 128, 2, 1, 4, wgrad_gemm_math(MT, false, 32)>), grid, block, 0, st, a);
   }
   MSL_CHECK_LAUNCH();
   // the piece reduce
-  // r06, k_wgrad_x6: S waves per 64 outputs, each summing every S-th piece (k_wsk_reduce_split), where a tile has >= 16
-  // pieces (the 16- and 9-tile layer3 1x1 / layer2 3x3 gradients: 32-56 chunks; at 8 pieces, 512 -> 2048, it lost 4 us)
-  const long long x6_pieces = pl.nchunk > 0 ? pl.nchunk : cdiv((long long)pl.nw, (long long)a.ntiles);
-  // 64 x 64, few tiles with many pieces each (the 33k-px 1x1 gradients: 4 tiles x ~128 pieces): 8 threads per
-  // output float4 (k_wsk_reduce_wide) instead of one serial chain of every piece
-  const long long sk_pieces = cdiv((long long)pl.nw, std::max(1LL, pl.T / pl.KS));  // per (tile, tap)
-  if (pl.rx6 && kWskSplit > 1 && x6_pieces >= kWskSplitMinPieces)
-    MSL_LAUNCH((k_wsk_reduce_split<128, 128, kWskSplit>), dim3(cdiv(128LL * 128 / 4 * taps, 64), rgrid.y),
-               dim3(64 * kWskSplit), 0, st, a);
-  else if (pl.bm == 128)
-    MSL_LAUNCH((k_wsk_reduce<128, 128>), rgrid, rblock, 0, st, a);
-  else if (pl.bm == 64 && (long long)rgrid.x * rgrid.y < 256 && sk_pieces >= 16)
-    MSL_LAUNCH((k_wsk_reduce_wide<64, 64, 8>), dim3(cdiv((long long)64 * 64 / 4 * taps, 32), rgrid.y), rblock, 0, st, a);
-  else if (pl.bm == 64)
-    MSL_LAUNCH((k_wsk_reduce<64, 64>), rgrid, rblock, 0, st, a);
-  else
-    MSL_LAUNCH((k_wsk_reduce<32, 128>), rgrid, rblock, 0, st, a);
+  switch (wgrad_reduce(pl, nbranch, taps)) {
+    case kWrSplit128:
+      MSL_LAUNCH((k_wsk_reduce_split<128, 128, kWskSplit>), dim3(cdiv(128LL * 128 / 4 * taps, 64), rgrid.y),
+                 dim3(64 * kWskSplit), 0, st, a);
+      break;
+    case kWrSk128: MSL_LAUNCH((k_wsk_reduce<128, 128>), rgrid, rblock, 0, st, a); break;
+    case kWrWide64:
+      MSL_LAUNCH((k_wsk_reduce_wide<64, 64, 8>), dim3(cdiv((long long)64 * 64 / 4 * taps, 32), rgrid.y), rblock, 0, st, a);
+      break;
+    case kWrSk64: MSL_LAUNCH((k_wsk_reduce<64, 64>), rgrid, rblock, 0, st, a); break;
+    case kWrSk32: MSL_LAUNCH((k_wsk_reduce<32, 128>), rgrid, rblock, 0, st, a); break;
+  }
   MSL_CHECK_LAUNCH();
   if (c.dbias) {
     MSL_LAUNCH(k_bias_grad, dim3(cout), block, 0, st, c.dy, P, c.dbias, cout, nbranch, c.accumulate);
@@ -1248,6 +1292,65 @@ int msl_conv_fwd_plan(int family, int nbranch, int taps, int cimg, int M, int P,
     info.T = pl.sched.T;
     info.split_img = pl.form.bform == kBPre ? 1 : 0;
   }
+  *out = info;
+  return MSL_OK;
+}
+
+int msl_conv_wgrad_plan(int family, int nbranch, int taps, int cin, int cout, int h, int w, int nimg, int has_dbias,
+                        int x_npart, int dy_npart, const msl_forms* forms, msl_conv_wgrad_plan_info* out) {
+  if (family < kFamF32 || family > kFamF16 || !out) return MSL_ERR_ARG;
+  const int math = family_math((Family)family, forms);
+  // the geometries of the entry points: 3x3 (one or two branches, with or without dbias), pointwise (neither)
+  if (math < 0 || bad_dims(nbranch, cin, cout, h, w, nimg) || x_npart < 0 || dy_npart < 0 ||
+      !(taps == 9 || (taps == 1 && nbranch == 1 && !has_dbias)))
+    return MSL_ERR_ARG;
+  const int P = nimg * h * w;
+  const int wr = taps == 1 ? P : w;  // a pointwise call passes one flat row (geom_1x1)
+  bool trans = false;
+  const WgradPlan pl = plan_wgrad_call(math, nbranch, taps, cin, cout, P, wr, has_dbias != 0, trans);
+  if (trans) {
+    std::swap(cin, cout);
+    std::swap(x_npart, dy_npart);
+  }
+  msl_conv_wgrad_plan_info info{};
+  info.gemm = pl.rx6 ? 1 : 0;
+  info.bm = pl.bm;
+  info.bn = pl.bn;
+  info.math = wgrad_gemm_math(math, pl.rx6, pl.bm);
+  info.split_rows = pl.rx6 ? 1 : 0;
+  info.reduce = (int)wgrad_reduce(pl, nbranch, taps);
+  info.trans = trans ? 1 : 0;
+  info.tiles_m = pl.tiles_m;
+  info.tiles_n = pl.tiles_n;
+  info.ntap = pl.ntap;
+  info.KS = pl.KS;
+  info.bk = pl.rx6 ? kWx6BK : kWskBK;
+  info.NW = pl.nw;
+  info.T = (int)pl.T;
+  info.slots = pl.slots;
+  info.nchunk = pl.nchunk;
+  info.kchunk = pl.kchunk;
+  info.swizzle = (pl.nw & 7) ? 0 : 1;
+  info.status = wgrad_refusal(pl, cin, cout, P);
+  // the longest run of K-steps of one tile in one worker's range, as the kernels cut them (sk_start)
+  long long run = 0;
+  if (pl.nchunk > 0) {
+    run = std::min(pl.KS, pl.kchunk);
+  } else if (info.status == MSL_OK) {
+    for (long long wk = 0; wk < pl.nw; ++wk) {
+      const long long b = wk * pl.T / pl.nw, e = (wk + 1) * pl.T / pl.nw;
+      if (e - b >= 2LL * pl.KS - 1) run = pl.KS;  // holds a whole tile
+      for (long long it = b; it < e && run < pl.KS;) {
+        const long long k_a = it % pl.KS, nst = std::min<long long>(pl.KS - k_a, e - it);
+        run = std::max(run, nst);
+        it += nst;
+      }
+    }
+  }
+  info.max_run = (int)run;
+  info.mask_tab = pl.rx6 && run + 3 <= kWxMaskTab ? 1 : 0;
+  if (pl.rx6 && wgrad_f16(math))  // counts none given: one per row, reduced by the call
+    info.rowscale = wgrad_rowscale(dy_npart ? dy_npart : cout, cout, x_npart ? x_npart : cin, cin);
   *out = info;
   return MSL_OK;
 }

@@ -60,6 +60,7 @@ SIGNATURES = {
     "msl_conv_fwd_form_count": (c_int, []),
     "msl_conv_fwd_form_describe": (c_int, [c_int, c_p]),
     "msl_conv_fwd_plan": (c_int, [c_int] * 8 + [c_p, c_p]),
+    "msl_conv_wgrad_plan": (c_int, [c_int] * 11 + [c_p, c_p]),
     "msl_dconv_fwd_bf16": (c_int, [c_p, c_p, c_p, c_p] + [c_int] * 8 + [c_p, c_p, c_sz, c_p]),
     "msl_dconv_dgrad_bf16": (c_int, [c_p, c_p, c_p] + [c_int] * 8 + [c_p, c_p, c_sz, c_p]),
     "msl_dconv_wgrad_bf16": (c_int, [c_p, c_p, c_p, c_p] + [c_int] * 9 + [c_p, c_p, c_sz, c_p]),
@@ -228,6 +229,22 @@ def conv_fwd_plan(family, nbranch, taps, cimg, m, p, accumulate, dil0, forms_=No
     fm = forms() if forms_ is None else ctypes.addressof(forms_)
     check(load(require_gpu=False).msl_conv_fwd_plan(family, nbranch, taps, cimg, m, p, accumulate, dil0, fm,
                                                     ctypes.addressof(out)), "msl_conv_fwd_plan")
+    return out
+
+
+class ConvWgradPlan(ctypes.Structure):
+    """msl_conv_wgrad_plan_info: the plan of one weight-gradient call (msl_conv_wgrad_plan; host only)."""
+    _fields_ = [(n, c_int) for n in ("gemm", "bm", "bn", "math", "split_rows", "reduce", "trans", "tiles_m", "tiles_n",
+                                     "ntap", "KS", "bk", "NW", "T", "slots", "nchunk", "kchunk", "swizzle", "max_run",
+                                     "mask_tab", "rowscale", "status")]
+
+
+def conv_wgrad_plan(family, nbranch, taps, cin, cout, h, w, nimg, has_dbias=0, x_npart=0, dy_npart=0, forms_=None):
+    """The plan of a weight-gradient call as a ConvWgradPlan (no GPU needed); `forms_` defaults to FORMS."""
+    out = ConvWgradPlan()
+    fm = forms() if forms_ is None else ctypes.addressof(forms_)
+    check(load(require_gpu=False).msl_conv_wgrad_plan(family, nbranch, taps, cin, cout, h, w, nimg, has_dbias, x_npart,
+                                                      dy_npart, fm, ctypes.addressof(out)), "msl_conv_wgrad_plan")
     return out
 
 
