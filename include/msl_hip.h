@@ -864,6 +864,67 @@ int msl_style_adain_coef(const float* content_stats, const float* style_stats, c
 int msl_style_output(const float* x, int x_grid, int h, int w, uint8_t* rgb_u8, float* seg_bgr, float mean_b,
                      float mean_g, float mean_r, msl_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Baseline JPEG decode, split between host and device (the reference's crosscity_Dataset.py:74
+ * `Image.open(image_path).convert("RGB")` on NTHU's 2048x1024 JPEGs).  The host parses the markers and
+ * Huffman-decodes the scan into quantised coefficients (serial); the device dequantises, runs libjpeg's
+ * JDCT_ISLOW inverse DCT, upsamples the chroma planes by libjpeg's fancy rules and converts YCbCr -> RGB
+ * (dense), byte-exact against libjpeg-turbo's defaults, i.e. against Pillow.
+ *
+ * Supported: 8-bit precision, SOF0 / SOF1 (Huffman), one interleaved scan of 3 components libjpeg takes for
+ * YCbCr (a JFIF marker; else an Adobe marker with transform 1; else component ids other than 'R','G','B')
+ * with luma sampling 1x1, 2x1 or 2x2 and both chroma 1x1 - or one grayscale component.  Every other valid
+ * file (progressive, arithmetic, lossless, hierarchical, 12-bit, 4 components, RGB-coded, other sampling
+ * factors, several scans, DNL) is MSL_ERR_SHAPE; a corrupt or truncated stream is MSL_ERR_ARG.  The two host
+ * entry points are thread-safe, keep no state, use no GPU, never read past file[n) and never write
+ * outside coef[0, coef_elems) and quant[0, 256).
+ * ---------------------------------------------------------------------- */
+typedef struct {
+  int32_t h, v;               /* sampling factors (a lone grayscale component is 1, 1 whatever the file says) */
+  int32_t tq;                 /* its quantisation table, 0..3 */
+  int32_t blocks_w, blocks_h; /* its block grid: whole MCUs, blocks_w = ceil(width / (8 hmax)) * h */
+  int32_t reserved;
+  int64_t offset;             /* of its first coefficient in the coefficient buffer, in int16 elements */
+} msl_jpeg_comp;
+
+typedef struct {
+  int32_t width, height;
+  int32_t ncomp;              /* 1 (grayscale) or 3 (YCbCr) */
+  int32_t hmax, vmax;         /* the luma sampling factors */
+  int32_t restart_interval;   /* MCUs between restart markers, 0 = none */
+  int32_t mcus_w, mcus_h;
+  msl_jpeg_comp comp[3];
+} msl_jpeg_header;
+
+/* Parse the markers up to the scan header and fill *header.  Host only. */
+int msl_jpeg_info(const uint8_t* file, size_t n, msl_jpeg_header* header);
+/* int16 elements of the coefficient buffer: 64 per block of every component, [comp][block row][block col][64]. */
+size_t msl_jpeg_coef_elems(const msl_jpeg_header* header);
+/* Parse, fill *header, Huffman-decode the scan into coef (HOST, caller-owned - a pinned staging buffer -
+ * coef_elems >= msl_jpeg_coef_elems elements, MSL_ERR_WORKSPACE if fewer): each block's 64 quantised
+ * coefficients in natural (de-zigzagged) order, the DC prediction resolved, restart markers honoured; and
+ * quant (HOST, uint16 [4][64], natural order; tables the file does not define are zero).  Host only. */
+int msl_jpeg_entropy_decode(const uint8_t* file, size_t n, msl_jpeg_header* header, int16_t* coef,
+                            size_t coef_elems, uint16_t* quant);
+/* Bytes of msl_jpeg_reconstruct's workspace: the components' uint8 planes of whole blocks. */
+size_t msl_jpeg_workspace(const msl_jpeg_header* header);
+/* coef / quant (DEVICE copies of what msl_jpeg_entropy_decode wrote, coef 16-byte aligned) -> rgb (DEVICE
+ * uint8 [height][width][3]), two launches on `stream`:
+ *   1. per 8x8 block: coefficient * table entry, libjpeg's jidctint.c (CONST_BITS 13, PASS1_BITS 2: the column
+ *      pass descaled by 11, the row pass by 18, DESCALE(x, n) = (x + (1 << (n-1))) >> n), clamp(x + 128, 0,
+ *      255), into the component's plane in ws;
+ *   2. per pixel: the chroma planes upsampled by libjpeg-turbo's fancy h2v1 / h2v2 rules (a chroma plane of
+ *      width <= 2 is box-replicated, as libjpeg selects), YCbCr -> RGB in libjpeg's 16-bit fixed point,
+ *      cropped to width x height; grayscale writes Y three times.
+ * Before any launch: MSL_ERR_ARG for a NULL pointer, a misaligned coef, a header that is not one
+ * msl_jpeg_info writes (sampling, tables, a block grid or offsets that disagree with the size) or
+ * ws_bytes < msl_jpeg_workspace(header); MSL_ERR_SHAPE above 2^28 pixels. */
+int msl_jpeg_reconstruct(const int16_t* coef, const uint16_t* quant, const msl_jpeg_header* header, uint8_t* rgb,
+                         void* ws, size_t ws_bytes, msl_stream_t stream);
+/* The kernels' tiles: 8x8 blocks per workgroup of launch 1, pixels per workgroup of launch 2. */
+int msl_jpeg_tile_blocks(void);
+int msl_jpeg_tile_pixels(void);
+
 /* Diagnostics (r06): the launch guard every entry point runs before each kernel launch (MSL_ERR_LAUNCH
  * when a block exceeds the kernel's __launch_bounds__).  Launches a 256-thread-bound probe kernel with
  * `threads` threads writing out[t] = t: MSL_OK (and out[0 .. threads) written) for 1 <= threads <= 256,

@@ -12,6 +12,13 @@ The augmentation draws (mirror, then x1, then y1, the reference's order) come fr
 `random.Random` the dataset owns and are made by the consumer in item order, so they do not
 depend on how many threads decode ahead (--data_loader_workers, at most 16; Pillow releases the
 GIL while decoding).
+
+A decoded image is an (H, W, 3) uint8 array - or, for a JPEG file (the NTHU cities of
+crosscity_Dataset.py, the lists of Client_dataset), the 1-D uint8 payload of the decode's host half
+(utils/jpeg.py: header, tables, Huffman-decoded coefficients), which goes through the same pinned
+staging slot and is finished on the device ahead of the transform.  The loader therefore asks the
+dataset for `item_plan(decoded)` and does not read a shape itself: for a payload the plan carries
+the header, (mirror, steps, header), and device_transform starts with image_of().
 """
 import collections
 import os
@@ -22,7 +29,7 @@ import numpy as np
 import torch
 
 from ..hip import MSLError
-from ..utils import preprocess, resample
+from ..utils import jpeg, preprocess, resample
 from ..utils.eval import name_classes  # noqa: F401  (the reference keeps the row names in this module)
 from ..utils.palette import label_colours, palette_table
 from ..utils.synthetic import IMG_MEAN
@@ -38,6 +45,37 @@ def _pil():
         raise MSLError("the file-backed datasets decode PNGs with Pillow, which is not installed; install "
                        "Pillow or leave --data_root_path unset for the synthetic loaders") from e
     return Image
+
+
+def decode_rgb(path, jpeg_decode="device", alloc=None):
+    """One image file for the device: a JPEG as the payload of its host half (utils/jpeg.py decode_file; the
+    device finishes it, utils/preprocess.py jpeg_reconstruct) - unless jpeg_decode is 'pillow' or the split
+    decoder refuses the file - anything else as Pillow's uint8 (H, W, 3) RGB array.  Either way the item is the
+    same bytes.  alloc(nbytes) -> a uint8 array: where a payload is decoded to (the loader's pinned staging slot;
+    default a new array).  Host only, thread-safe."""
+    if jpeg_decode == "device" and str(path).lower().endswith(jpeg.EXTENSIONS):
+        payload = jpeg.decode_file(path, alloc)
+        if payload is not None:
+            return payload
+    with _pil().open(path) as im:
+        return np.asarray(im.convert("RGB"), np.uint8)
+
+
+def image_of(rgb, plan):
+    """(the decoded image on the device, (mirror, steps)): an item_plan that carries a JPEG header says `rgb` is
+    the payload on the device, finished here."""
+    if len(plan) == 3:
+        return preprocess.jpeg_reconstruct(rgb, plan[2]), plan[:2]
+    return rgb, plan
+
+
+def _item_plan(self, rgb):
+    """The plan of a decoded item.  An (H, W, 3) array says its own size; a JPEG payload (1-D) says it in
+    its header, which then rides with the plan: (mirror, steps, header)."""
+    if jpeg.is_payload(rgb):
+        header = jpeg.header_of(rgb)
+        return tuple(self.plan(header.width, header.height)) + (header,)
+    return self.plan(rgb.shape[1], rgb.shape[0])
 
 
 def _pair(v):
@@ -121,6 +159,8 @@ class City_Dataset:
                 steps.append((self.base_size, self._draw_crop(w, h)))
         return mirror, steps or [((w, h), None)]
 
+    item_plan = _item_plan
+
     def _draw_crop(self, w, h):
         cw, ch = self.crop_size
         x1 = self.rng.randint(0, w - cw)
@@ -157,9 +197,10 @@ class City_Dataset:
 
     def __getitem__(self, item):
         rgb, ids = self.decode(item)
-        plan = self.plan(rgb.shape[1], rgb.shape[0])
+        plan = self.item_plan(rgb)
         dev = self._device()
-        img, lab = self.device_transform(torch.from_numpy(rgb).to(dev), torch.from_numpy(ids).to(dev), plan)
+        img, lab = self.device_transform(torch.from_numpy(rgb).to(dev),
+                                         None if ids is None else torch.from_numpy(ids).to(dev), plan)
         return img, lab, self.paths(item)[2]
 
 
@@ -169,6 +210,15 @@ class _Slot:
 
     def __init__(self):
         self.rgb = self.ids = self.event = None
+
+    def reserve(self, nbytes):
+        """uint8 (nbytes,) numpy view of the pinned image buffer, for a decoder that writes its output in place
+        (a dataset's decode_into); fill() then finds the item where it belongs and copies nothing."""
+        if self.event is not None:
+            self.event.synchronize()
+        if self.rgb is None or self.rgb.numel() < nbytes:
+            self.rgb = torch.empty(int(nbytes), dtype=torch.uint8).pin_memory()
+        return self.rgb[:nbytes].numpy()
 
     def fill(self, rgb, ids):
         if self.event is not None:
@@ -183,7 +233,8 @@ class _Slot:
                 buf = torch.empty(arr.size, dtype=torch.uint8).pin_memory()
                 setattr(self, name, buf)
             view = buf[:arr.size].view(arr.shape)
-            np.copyto(view.numpy(), arr)
+            if arr.ctypes.data != buf.data_ptr():  # (else: decoded in place, reserve())
+                np.copyto(view.numpy(), arr)
             out.append(view)
         return out
 
@@ -210,7 +261,11 @@ class DeviceLoader:
         return idx
 
     def _decode(self, item, slot):
-        rgb, ids = self.dataset.decode(item)
+        into = getattr(self.dataset, "decode_into", None)
+        if slot is not None and into is not None:
+            rgb, ids = into(item, slot.reserve)  # the image may already sit in the slot's pinned buffer
+        else:
+            rgb, ids = self.dataset.decode(item)
         return slot.fill(rgb, ids) if slot is not None else (rgb, ids)
 
     def host_items(self, staged=False):
@@ -234,7 +289,7 @@ class DeviceLoader:
                         nxt += 1
                     got = pending.popleft().result()
                 rgb, ids = got
-                plan = self.dataset.plan(rgb.shape[1], rgb.shape[0])
+                plan = self.dataset.item_plan(rgb)
                 yield rgb, ids, plan, self.dataset.paths(item)[2], slot_of(seq)
         finally:
             for f in pending:
@@ -331,24 +386,25 @@ class Client_dataset:
         path = self.items[item]
         return path, None, os.path.splitext(os.path.basename(path))[0]
 
-    def decode(self, item):
-        Image = _pil()
-        with Image.open(self.paths(item)[0]) as im:
-            return np.asarray(im.convert("RGB"), np.uint8), None
+    def decode(self, item, alloc=None):
+        return decode_rgb(self.paths(item)[0], getattr(self.args, "jpeg_decode", "device"), alloc), None
+
+    decode_into = decode  # (item, alloc): a JPEG's payload is decoded straight into the staging slot
 
     def plan(self, w, h):
         return False, [(self.rsize if self.resize else (w, h), None)]
 
+    item_plan = _item_plan
+
     def device_transform(self, rgb, ids, plan):
-        mirror, steps = plan
+        rgb, (mirror, steps) = image_of(rgb, plan)
         return preprocess.resize_image(rgb, steps[0][0], None, mirror), None
 
     _device = City_Dataset._device
 
     def __getitem__(self, item):
         rgb, _ = self.decode(item)
-        img, _ = self.device_transform(torch.from_numpy(rgb).to(self._device()), None,
-                                       self.plan(rgb.shape[1], rgb.shape[0]))
+        img, _ = self.device_transform(torch.from_numpy(rgb).to(self._device()), None, self.item_plan(rgb))
         return img, None, self.paths(item)[2]
 
 

@@ -118,6 +118,13 @@ SIGNATURES = {
     "msl_resize_nearest_label": (c_int, [c_p] + [c_int] * 7 + [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p]),
     "msl_png_unfilter_lane": (c_int, [c_p, c_int, c_int, c_int, c_int, c_sz, c_p, c_p]),
     "msl_png_unfilter_band_rows": (c_int, []),
+    "msl_jpeg_info": (c_int, [c_p, c_sz, c_p]),
+    "msl_jpeg_coef_elems": (c_sz, [c_p]),
+    "msl_jpeg_entropy_decode": (c_int, [c_p, c_sz, c_p, c_p, c_sz, c_p]),
+    "msl_jpeg_workspace": (c_sz, [c_p]),
+    "msl_jpeg_reconstruct": (c_int, [c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "msl_jpeg_tile_blocks": (c_int, []),
+    "msl_jpeg_tile_pixels": (c_int, []),
     "msl_im2col": (c_int, [c_p] + [c_int] * 11 + [c_p, c_p]),
     "msl_col2im": (c_int, [c_p] + [c_int] * 11 + [c_p, c_p]),
     "msl_maxpool_fwd": (c_int, [c_p] + [c_int] * 8 + [c_p, c_p, c_p]),
@@ -210,6 +217,18 @@ def ptr(t):
 class Forms(ctypes.Structure):
     """msl_forms (include/msl_hip.h): the kernel forms every conv / pack / BN call takes (ABI 3)."""
     _fields_ = [("f32_form", c_int), ("sk_hybrid", c_int), ("pack_form", c_int), ("bn_fused", c_int)]
+
+
+class JpegComp(ctypes.Structure):
+    """msl_jpeg_comp: one component of a msl_jpeg_header."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("h", "v", "tq", "blocks_w", "blocks_h", "reserved")] + [
+        ("offset", ctypes.c_int64)]
+
+
+class JpegHeader(ctypes.Structure):
+    """msl_jpeg_header: what msl_jpeg_info / msl_jpeg_entropy_decode say about a file (utils/jpeg.py)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "ncomp", "hmax", "vmax", "restart_interval",
+                                              "mcus_w", "mcus_h")] + [("comp", JpegComp * 3)]
 
 
 class ConvForm(ctypes.Structure):

@@ -369,10 +369,11 @@ class UDATrainer(Trainer):
                          float(self.loss_seg_value), float(self.loss_target_value))
 
 
-def add_UDA_train_args(arg_parser):
-    """solve_gta5.py:407-432."""
+def add_UDA_train_args(arg_parser, source_datasets=("gta5", "synthia")):
+    """solve_gta5.py:407-432.  source_datasets: the choices of --source_dataset, the first the default
+    (tools/solve_crosscity.py passes its own)."""
     a = arg_parser.add_argument
-    a("--source_dataset", default="gta5", type=str, choices=["gta5", "synthia"])
+    a("--source_dataset", default=source_datasets[0], type=str, choices=list(source_datasets))
     a("--source_split", default="train", type=str)
     for dom in ("source", "target"):
         a(f"--{dom}_data_path", type=str, default=None,

@@ -72,10 +72,11 @@ def _free_port():
 def dataset_paths(dataset, data_root_path, list_path, gt_path=None):
     """The {data_root_path, list_path, gt_path} of one file-backed dataset.  Without a gt path the
     reference's layout (train_source.py:27-60): Cityscapes <root>/gtFine beside the images'
-    <root>/leftImg8bit..., GTA5 <root>/labels, SYNTHIA <root>/GT/LABELS (synthia_Dataset.py:51); the list
-    path defaults to the data root."""
+    <root>/leftImg8bit..., GTA5 <root>/labels, SYNTHIA <root>/GT/LABELS (synthia_Dataset.py:51), a cross-city
+    tree <root>/Labels/Test (crosscity_Dataset.py:47); the list path defaults to the data root."""
     if gt_path is None:
-        sub = {"gta5": "labels", "synthia": os.path.join("GT", "LABELS")}.get(str(dataset).lower(), "gtFine")
+        sub = {"gta5": "labels", "synthia": os.path.join("GT", "LABELS"),
+               "crosscity": os.path.join("Labels", "Test")}.get(str(dataset).lower(), "gtFine")
         gt_path = os.path.join(data_root_path, sub)
     return {"data_root_path": data_root_path, "list_path": list_path or data_root_path, "gt_path": gt_path}
 
@@ -324,6 +325,10 @@ def add_train_args(arg_parser):
     a("--num_classes", default=19, type=int)
     a("--data_loader_workers", default=0, type=int,
       help="threads that decode PNGs ahead of the step (file-backed datasets; at most 16)")
+    a("--jpeg_decode", default="device", choices=["device", "pillow"],
+      help="JPEG images (the NTHU cities, tools/predict.py lists): device = Huffman-decode on the decoding "
+           "threads, inverse DCT, upsampling and colour conversion on the GPU (byte-exact against Pillow; files "
+           "that decoder refuses go through Pillow); pillow = Pillow decodes the whole file (not in the reference)")
     a("--pin_memory", default=2, type=int)
     a("--split", type=str, default="train")
     a("--random_mirror", default=True, type=str2bool)

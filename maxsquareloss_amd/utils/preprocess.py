@@ -16,12 +16,18 @@ two transforms.
 
 png_unfilter undoes the PNG scanline filters of one byte lane on the device (csrc/png.hip): SYNTHIA's
 16-bit label PNGs are inflated on the host (utils/png.py) and reconstructed here, ahead of resize_label.
+
+jpeg_reconstruct finishes a baseline JPEG whose scan the host Huffman-decoded (utils/jpeg.py decode_file):
+dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB on the device (csrc/jpeg.hip), the uint8
+(H, W, 3) image Pillow decodes, ahead of resize_image.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from .. import hip
-from . import resample
+from . import jpeg, resample
 from .synthetic import IMG_MEAN
 
 # id -> trainId tables of the three loaders (values not listed map to the ignore label -1)
@@ -212,4 +218,33 @@ def png_unfilter(plane_or_scan, bpp=1, lane=0):
     out = torch.empty((h, w), dtype=torch.uint8, device=t.device)
     hip.check(hip.load().msl_png_unfilter_lane(t.data_ptr(), h, w, bpp, lane, t.stride(0), out.data_ptr(),
                                                hip.stream_ptr()), "msl_png_unfilter_lane")
+    return out
+
+
+# ---------------------------------------------------------------------------- JPEG reconstruction (NTHU images)
+def jpeg_reconstruct(payload, header=None):
+    """The device half of the JPEG decode (csrc/jpeg.hip, two launches on the current stream).  payload: the
+    CUDA uint8 1-D tensor utils/jpeg.py decode_file made on the host - header, tables, coefficients.  header:
+    the payload's hip.JpegHeader as read on the host (utils/jpeg.py header_of; the loaders pass it with the
+    item's plan); without it the header's bytes are copied back from the device, which waits for the stream.
+    Returns CUDA uint8 (H, W, 3) RGB, what utils/jpeg.py reconstruct gives on the host and Pillow for the file."""
+    t = payload
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() <= jpeg.COEF_AT:
+        raise hip.MSLError("jpeg_reconstruct: expected a CUDA uint8 1-D payload (utils/jpeg.py decode_file)")
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    if header is None:
+        header = jpeg.header_of(t[:jpeg.HEADER_BYTES].cpu())
+    lib = hip.load()
+    hp = ctypes.addressof(header)
+    elems = lib.msl_jpeg_coef_elems(hp)
+    if elems == 0 or t.numel() < jpeg.COEF_AT + 2 * elems:
+        raise hip.MSLError(f"jpeg_reconstruct: a payload of {t.numel()} bytes does not hold the {elems} coefficients "
+                           "of its header")
+    ws_bytes = lib.msl_jpeg_workspace(hp)
+    ws = hip.workspace(ws_bytes, t.device)
+    out = torch.empty((header.height, header.width, 3), dtype=torch.uint8, device=t.device)
+    hip.check(lib.msl_jpeg_reconstruct(t.data_ptr() + jpeg.COEF_AT, t.data_ptr() + jpeg.HEADER_BYTES, hp,
+                                       out.data_ptr(), ws.data_ptr(), ws_bytes, hip.stream_ptr()),
+              "msl_jpeg_reconstruct")
     return out
