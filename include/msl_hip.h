@@ -635,6 +635,18 @@ int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi,
                    const long long* label, unsigned long long* confusion, int32_t* argmax_out,
                    msl_stream_t stream);
 
+/* msl_predict_up without flip, followed by the reference's Trainer.rectification with both of its crops, in one
+ * launch.  crop0 / crop1 are the low-resolution logits [c][hi][wi] of the half-size windows at x0 = 0 and
+ * x0 = W0 / 2 of the original image, magnified to full size, stylised and forwarded.  Per pixel (y, x) of
+ * ho x wo: m, cls = the maximum and its first index of up(base); inside rows segy0 <= y < segy0 + ho/2, with
+ * k = x / (wo/2), m', cls' = the same of up(crop_k) at (2 (y - segy0), 2 (x - k wo/2)) - the reference's
+ * nearest x1/2 of the crop's prediction - and cls = cls' where m' > m (logits, strict; a NaN on either side
+ * keeps cls, as numpy's > does).  Outputs as msl_predict_up.  MSL_ERR_ARG: odd ho or wo, segy0 outside
+ * [0, ho/2], c > 32, and msl_predict_up's argument errors. */
+int msl_predict_rectify(const float* base, const float* crop0, const float* crop1, int c, int hi, int wi, int ho,
+                        int wo, int segy0, const long long* label, unsigned long long* confusion,
+                        int32_t* argmax_out, msl_stream_t stream);
+
 /* msl_predict_up's decision written as images, in the same single pass (inputs, label / confusion and
  * the class as there; all maps uint8, all nullable, at least one of them or the confusion matrix required):
  *   class_out  [ho*wo]    the class, the value msl_predict_up writes to argmax_out;
@@ -863,6 +875,39 @@ int msl_style_adain_coef(const float* content_stats, const float* style_stats, c
  *            Trainer.seg_transform, the segmentation network's input */
 int msl_style_output(const float* x, int x_grid, int h, int w, uint8_t* rgb_u8, float* seg_bgr, float mean_b,
                      float mean_g, float mean_r, msl_stream_t stream);
+
+/* In-loop domain adaptation (the reference's tools/ADAIN.py; cropTrans, Trainer.seg_transform and
+ * Trainer.rectification of tools/train_source.py): what sits between the style network and the segmentation
+ * network.  "torch-nearest" below is F.interpolate's default mode: the source index of destination d on an
+ * axis resized from `in` to `out` cells is min((int)floorf(d * scale), in - 1), scale = (float)in / (float)out
+ * formed in fp32 by these entry points, the product one rounded fp32 multiply.  One image per call, on the
+ * stream, no host sync, no atomics; arguments are checked before any launch.
+ *
+ * msl_style_input reading the window (x0, y0, cw, ch) of an ih x iw image (uint8 [ih][iw][3] or float
+ * [3][ih][iw], exactly one of them), magnified to h x w by torch-nearest: the grid y[cpad][h+2][w+2], bit for
+ * bit msl_style_input of the gathered image.  MSL_ERR_ARG: a window outside the image; MSL_ERR_SHAPE: h or
+ * w below 2. */
+int msl_style_input_window(const uint8_t* rgb_u8, const float* chw_f32, int ih, int iw, int x0, int y0, int cw,
+                           int ch, int h, int w, const float* w1, const float* b1, float* y, int cpad,
+                           msl_stream_t stream);
+/* msl_style_output's seg_bgr of the h x w map x, gathered by torch-nearest into the window (dx0, dy0, dw, dh)
+ * of seg_bgr[3][hd][wd]; cells outside the window are not written.
+ *   one map  (full_h = full_w = 0; mid = (dh, dw), off = 0): the window is x resized to dh x dw - the
+ *            reference's seg_transform when seg_size != base_size;
+ *   two maps (full_h, full_w > 0): x is first resized to mid_h x mid_w and placed at (off_y, off_x) of a
+ *            stitched map of full_h x full_w, which is then resized to hd x wd - cropTrans followed by
+ *            seg_transform, the indices composed.  A window cell whose stitched source lies outside this
+ *            image's mid_h x mid_w part is left alone, so the window may be any cover of the image's share.
+ * The quantisation is pointwise and commutes with the gather: the values are those of interpolate, then
+ * mul(255).add(0.5).clamp(0, 255), minus the mean, in B, G, R.  MSL_ERR_ARG: a window outside the
+ * destination, a part outside the stitched map, one map with mid != (dh, dw). */
+int msl_style_output_resampled(const float* x, int x_grid, int h, int w, int mid_h, int mid_w, int full_h, int full_w,
+                               int off_y, int off_x, float* seg_bgr, int hd, int wd, int dx0, int dy0, int dw, int dh,
+                               float mean_b, float mean_g, float mean_r, msl_stream_t stream);
+/* out[ho][wo] = label[h][w] resized by torch-nearest (int64 trainIds; the reference interpolates its float
+ * label map in seg_transform). */
+int msl_label_resize_nearest(const long long* label, int h, int w, long long* out, int ho, int wo,
+                             msl_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Baseline JPEG decode, split between host and device (the reference's crosscity_Dataset.py:74

@@ -905,6 +905,61 @@ __global__ void __launch_bounds__(256) k_predict_up(const float* __restrict__ L,
   }
 }
 
+// k_predict_up without flip, then the reference's Trainer.rectification (tools/train_source.py:353-381)
+// with both of its crops: inside rows [segy0, segy0 + Ho/2) the pixel (y, x) also has a prediction from
+// crop k = x / (Wo/2), the half-size window magnified, stylised and forwarded on its own, at
+// (2 (y - segy0), 2 (x - k Wo/2)) of its upsampled logits (the reference's nearest x1/2 of that map is
+// [::2, ::2]).  The crop's class replaces the pixel's where its winning logit is strictly greater
+// (numpy's >: a NaN on either side keeps the class).  v is reused for the crop: one pixel's registers.
+template <int CM>
+__global__ void __launch_bounds__(256) k_predict_rectify(const float* __restrict__ L,
+                                                          const float* __restrict__ L0,
+                                                          const float* __restrict__ L1, Geo g, int segy0,
+                                                          const long long* __restrict__ label,
+                                                          unsigned long long* __restrict__ cm,
+                                                          int32_t* __restrict__ arg) {
+  __shared__ unsigned int h[kMaxC * kMaxC];
+  const int cc = g.C * g.C;
+  if (cm) {
+    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
+    __syncthreads();
+  }
+  const int hh = g.Ho >> 1, hw = g.Wo >> 1;
+  const long long npx = (long long)g.Ho * g.Wo;  // < 2^31 (geo_ok); the stride may step past it
+  for (long long pp = blockIdx.x * 256LL + threadIdx.x; pp < npx; pp += (long long)gridDim.x * 256) {
+    const int px = (int)pp;
+    const int oy = px / g.Wo, ox = px - oy * g.Wo;
+    float v[CM];
+    up_logits<CM>(L, g, lin(oy, g.sh, g.Hi), lin(ox, g.sw, g.Wi), v);
+    int best = argmax_np<CM>(v, g.C);
+    if (oy >= segy0 && oy < segy0 + hh) {
+      float m = v[0];  // the value at the class: the maximum, or the first NaN (np.amax)
+#pragma unroll
+      for (int c = 1; c < CM; ++c)
+        if (c == best) m = v[c];
+      const int k = ox >= hw ? 1 : 0;
+      const int yy = 2 * (oy - segy0), xx = 2 * (ox - k * hw);
+      up_logits<CM>(k ? L1 : L0, g, lin(yy, g.sh, g.Hi), lin(xx, g.sw, g.Wi), v);
+      const int nb = argmax_np<CM>(v, g.C);
+      float nm = v[0];
+#pragma unroll
+      for (int c = 1; c < CM; ++c)
+        if (c == nb) nm = v[c];
+      if (nm > m) best = nb;
+    }
+    if (arg) arg[px] = best;
+    if (cm) {
+      const long long y = label[px];
+      if (y >= 0 && y < g.C) atomicAdd(&h[(int)y * g.C + best], 1u);
+    }
+  }
+  if (cm) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < cc; i += 256)
+      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
+  }
+}
+
 // ---------------------------------------------------------------- evaluation: prediction images
 struct ImgOut {
   uint8_t* cls;     // [Ho*Wo]   the class (k_predict_up's arg as a byte)
@@ -1389,6 +1444,21 @@ int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi,
     MSL_DISPATCH_C(c, CM,
                    MSL_LAUNCH((k_predict_up<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
                               g, label, confusion, argmax_out));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_predict_rectify(const float* base, const float* crop0, const float* crop1, int c, int hi, int wi, int ho,
+                        int wo, int segy0, const long long* label, unsigned long long* confusion,
+                        int32_t* argmax_out, msl_stream_t stream) {
+  if (!geo_ok(c, hi, wi, ho, wo) || !base || !crop0 || !crop1 || (label == nullptr) != (confusion == nullptr) ||
+      (!confusion && !argmax_out) || (ho & 1) || (wo & 1) || segy0 < 0 || segy0 > ho / 2)
+    return MSL_ERR_ARG;
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * wo, 256));
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_predict_rectify<CM>), dim3(nblk), dim3(256), 0, as_stream(stream), base, crop0,
+                            crop1, g, segy0, label, confusion, argmax_out));
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

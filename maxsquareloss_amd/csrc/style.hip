@@ -114,6 +114,50 @@ __global__ void __launch_bounds__(kStyleThreads) k_style_input(const uint8_t* __
   for (int o = 3; o < cpad; ++o) y[(long long)o * plane_total + i] = 0.f;
 }
 
+// torch's `nearest` source index (F.interpolate's default mode): min((int)floorf(dst * scale), n - 1) with
+// scale = (float)in / (float)out formed by the host; one fp32 multiply, rounded, then the floor (no FMA:
+// contraction is off in this file).  Not dst * in / out in integers: 24 -> 74 and 56 -> 46 differ.
+__device__ __forceinline__ int nearest_t(int dst, float scale, int n) {
+  const int s = (int)floorf((float)dst * scale);
+  return s < n - 1 ? s : n - 1;
+}
+
+struct Window {
+  int x0, y0, cw, ch;  // the window of the source image
+  float sx, sy;        // cw / w and ch / h
+};
+
+// k_style_input reading a window of the image magnified to h x w by torch's nearest rule: the reference's
+// F.interpolate(crop, size) ahead of the style network (cropTrans, rectification), never materialised.
+// iw is the image's row length, ihw its plane.
+__global__ void __launch_bounds__(kStyleThreads) k_style_input_window(const uint8_t* __restrict__ u8,
+                                                                      const float* __restrict__ f32, int iw,
+                                                                      long long ihw, Window win, int h, int w,
+                                                                      const float* __restrict__ w1,
+                                                                      const float* __restrict__ b1,
+                                                                      float* __restrict__ y, int cpad,
+                                                                      int plane_total) {
+  const int i = blockIdx.x * kStyleThreads + threadIdx.x;
+  if (i >= plane_total) return;
+  const int gw = w + 2;
+  const int col = i % gw, row = i / gw;
+  const int sy = win.y0 + nearest_t(reflect1(row, h), win.sy, win.ch);
+  const int sx = win.x0 + nearest_t(reflect1(col, w), win.sx, win.cw);
+  const long long px = (long long)sy * iw + sx;
+  float v[3];
+  if (u8) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = __fdiv_rn((float)u8[px * 3 + k], 255.f);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = f32[k * ihw + px];
+  }
+#pragma unroll
+  for (int o = 0; o < 3; ++o)
+    y[(long long)o * plane_total + i] = fmaf(w1[3 * o + 2], v[2], fmaf(w1[3 * o + 1], v[1], fmaf(w1[3 * o], v[0], b1[o])));
+  for (int o = 3; o < cpad; ++o) y[(long long)o * plane_total + i] = 0.f;
+}
+
 // ------------------------------------------------------------------------------------------ statistics
 // (count, mean, M2 = sum of squared deviations from that mean) of a set of values; two sets merge by Chan
 // et al.'s update, which never forms a difference of large sums: a channel with mean 1000 and spread 0.01
@@ -290,8 +334,66 @@ __global__ void __launch_bounds__(kStyleThreads) k_style_output(StyleSrc s, int 
   }
 }
 
+// One axis of k_style_output_resampled: a destination coordinate d (absolute, inside the window) to a row
+// or column of the decoder's map.
+//   one map  (full == 0): l = d - d0, the window's own coordinate, over `mid` cells;
+//   two maps (full  > 0): l = nearest(d: full -> dest) - off, the cell of the stitched map of `full` cells
+//                         this image holds `mid` of, from `off` on; outside [0, mid) the pixel is another
+//                         image's and is left alone;
+// then nearest(l: n -> mid), n the decoder map's size.
+struct AxisMap {
+  int d0, mid, full, off, n;
+  float s_in, s_out;  // n / mid, full / dest
+};
+
+__device__ __forceinline__ int axis_src(const AxisMap& a, int d) {
+  const int l = a.full ? nearest_t(d, a.s_out, a.full) - a.off : d - a.d0;
+  if (l < 0 || l >= a.mid) return -1;
+  return nearest_t(l, a.s_in, a.n);
+}
+
+// k_style_output's seg output gathered through torch's nearest maps into the window (ax.d0, ay.d0, dw, dh)
+// of seg[3][hd][wd]: the quantisation is pointwise, so it commutes with the gather and the values are
+// those of interpolate -> mul, add, clamp -> minus mean -> B, G, R.
+__global__ void __launch_bounds__(kStyleThreads) k_style_output_resampled(StyleSrc s, AxisMap ay, AxisMap ax, int dw,
+                                                                          int npx, float* __restrict__ seg, int wd,
+                                                                          long long dplane, float mean_b,
+                                                                          float mean_g, float mean_r) {
+  const int i = blockIdx.x * kStyleThreads + threadIdx.x;
+  if (i >= npx) return;
+  const int r = i / dw, c = i - r * dw;
+  const int dy = ay.d0 + r, dx = ax.d0 + c;
+  const int sy = axis_src(ay, dy), sx = axis_src(ax, dx);
+  if (sy < 0 || sx < 0) return;
+  float q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float v = s.x[k * s.plane + (long long)sy * s.pitch + sx] * 255.f;
+    v = v + 0.5f;
+    v = v < 0.f ? 0.f : v;
+    q[k] = v > 255.f ? 255.f : v;
+  }
+  const long long o = (long long)dy * wd + dx;
+  seg[o] = q[2] - mean_b;
+  seg[dplane + o] = q[1] - mean_g;
+  seg[2 * dplane + o] = q[0] - mean_r;
+}
+
+// out[ho][wo] = in[nearest][nearest]: F.interpolate of the reference's float label map, on the int64 map
+__global__ void __launch_bounds__(kStyleThreads) k_label_resize_nearest(const long long* __restrict__ in, int h, int w,
+                                                                        long long* __restrict__ out, int wo, int npx,
+                                                                        float sy, float sx) {
+  const int i = blockIdx.x * kStyleThreads + threadIdx.x;
+  if (i >= npx) return;
+  const int r = i / wo, c = i - r * wo;
+  out[i] = in[(long long)nearest_t(r, sy, h) * w + nearest_t(c, sx, w)];
+}
+
 // every index a kernel forms from these counts stays below 2^31
 static inline bool fits_i32(long long v) { return v > 0 && v <= 0x7fffffffLL; }
+
+// torch's scale of a nearest map from `in` to `out` cells: compute_scales_value<float>
+static inline float nearest_scale(int in, int out) { return (float)in / (float)out; }
 
 }  // namespace msl
 
@@ -333,6 +435,22 @@ int msl_style_input(const uint8_t* rgb_u8, const float* chw_f32, int h, int w, c
   if (!fits_i32(plane * cpad)) return MSL_ERR_ARG;
   MSL_LAUNCH(k_style_input, dim3((unsigned)cdiv(plane, kStyleThreads)), dim3(kStyleThreads), 0, as_stream(stream),
              rgb_u8, chw_f32, h, w, w1, b1, y, cpad, (int)plane);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_style_input_window(const uint8_t* rgb_u8, const float* chw_f32, int ih, int iw, int x0, int y0, int cw,
+                           int ch, int h, int w, const float* w1, const float* b1, float* y, int cpad,
+                           msl_stream_t stream) {
+  if ((rgb_u8 == nullptr) == (chw_f32 == nullptr) || !w1 || !b1 || !y || cpad < 3 || h < 1 || w < 1 || ih < 1 ||
+      iw < 1 || x0 < 0 || y0 < 0 || cw < 1 || ch < 1 || (long long)x0 + cw > iw || (long long)y0 + ch > ih)
+    return MSL_ERR_ARG;
+  if (h < 2 || w < 2) return MSL_ERR_SHAPE;
+  const long long plane = (h + 2LL) * (w + 2LL);
+  if (!fits_i32(plane * cpad) || !fits_i32(3LL * ih * iw)) return MSL_ERR_ARG;
+  const Window win = {x0, y0, cw, ch, nearest_scale(cw, w), nearest_scale(ch, h)};
+  MSL_LAUNCH(k_style_input_window, dim3((unsigned)cdiv(plane, kStyleThreads)), dim3(kStyleThreads), 0,
+             as_stream(stream), rgb_u8, chw_f32, iw, (long long)ih * iw, win, h, w, w1, b1, y, cpad, (int)plane);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }
@@ -385,6 +503,42 @@ int msl_style_output(const float* x, int x_grid, int h, int w, uint8_t* rgb_u8, 
   if (!fits_i32(3 * (h + 2LL) * (w + 2LL))) return MSL_ERR_ARG;
   MSL_LAUNCH(k_style_output, dim3((unsigned)cdiv(hw, kStyleThreads)), dim3(kStyleThreads), 0, as_stream(stream),
              style_src(x, x_grid, h, w), w, (int)hw, rgb_u8, seg_bgr, mean_b, mean_g, mean_r);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_style_output_resampled(const float* x, int x_grid, int h, int w, int mid_h, int mid_w, int full_h, int full_w,
+                               int off_y, int off_x, float* seg_bgr, int hd, int wd, int dx0, int dy0, int dw, int dh,
+                               float mean_b, float mean_g, float mean_r, msl_stream_t stream) {
+  if (!x || !seg_bgr || h < 1 || w < 1 || (unsigned)x_grid > 1u || mid_h < 1 || mid_w < 1 || hd < 1 || wd < 1 ||
+      dx0 < 0 || dy0 < 0 || dw < 1 || dh < 1 || (long long)dx0 + dw > wd || (long long)dy0 + dh > hd)
+    return MSL_ERR_ARG;
+  const bool two = full_h != 0 || full_w != 0;
+  if (two) {
+    if (full_h < 1 || full_w < 1 || off_y < 0 || off_x < 0 || (long long)off_y + mid_h > full_h ||
+        (long long)off_x + mid_w > full_w)
+      return MSL_ERR_ARG;
+  } else if (mid_h != dh || mid_w != dw || off_y != 0 || off_x != 0) {
+    return MSL_ERR_ARG;
+  }
+  if (!fits_i32(3 * (h + 2LL) * (w + 2LL)) || !fits_i32(3LL * hd * wd)) return MSL_ERR_ARG;
+  const AxisMap ay = {dy0, mid_h, full_h, off_y, h, nearest_scale(h, mid_h), two ? nearest_scale(full_h, hd) : 0.f};
+  const AxisMap ax = {dx0, mid_w, full_w, off_x, w, nearest_scale(w, mid_w), two ? nearest_scale(full_w, wd) : 0.f};
+  const long long npx = (long long)dw * dh;
+  MSL_LAUNCH(k_style_output_resampled, dim3((unsigned)cdiv(npx, kStyleThreads)), dim3(kStyleThreads), 0,
+             as_stream(stream), style_src(x, x_grid, h, w), ay, ax, dw, (int)npx, seg_bgr, wd, (long long)hd * wd,
+             mean_b, mean_g, mean_r);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_label_resize_nearest(const long long* label, int h, int w, long long* out, int ho, int wo,
+                             msl_stream_t stream) {
+  if (!label || !out || h < 1 || w < 1 || ho < 1 || wo < 1) return MSL_ERR_ARG;
+  const long long npx = (long long)ho * wo;
+  if (!fits_i32(npx) || !fits_i32((long long)h * w)) return MSL_ERR_ARG;
+  MSL_LAUNCH(k_label_resize_nearest, dim3((unsigned)cdiv(npx, kStyleThreads)), dim3(kStyleThreads), 0,
+             as_stream(stream), label, h, w, out, wo, (int)npx, nearest_scale(h, ho), nearest_scale(w, wo));
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

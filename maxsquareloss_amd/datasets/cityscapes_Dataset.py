@@ -179,11 +179,14 @@ class City_Dataset:
         return img, lab
 
     def device_transform(self, rgb, ids, plan):
-        """rgb / ids: the decoded uint8 tensors on the GPU -> ((1,3,H,W) fp32, (1,H,W) int64)."""
+        """rgb / ids: the decoded uint8 tensors on the GPU -> ((1,3,H,W) fp32, (1,H,W) int64).  With
+        self.deliver_uint8 (set by tools/ADAIN.py, whose style network reads RGB bytes: the reference's
+        adain_transform) the image stays the resized uint8 (H, W, 3) RGB."""
         mirror, steps = plan
+        keep_u8 = getattr(self, "deliver_uint8", False)
         for k, (out_wh, crop) in enumerate(steps):
             last = k == len(steps) - 1
-            rgb = preprocess.resize_image(rgb, out_wh, crop, mirror, as_uint8=not last)
+            rgb = preprocess.resize_image(rgb, out_wh, crop, mirror, as_uint8=keep_u8 or not last)
             ids = preprocess.resize_label(ids, out_wh, self.lut if last else None, crop, mirror)
             mirror = False
         return rgb, ids

@@ -150,6 +150,10 @@ SIGNATURES = {
     "msl_style_max_styles": (c_int, []),
     "msl_style_adain_coef": (c_int, [c_p, c_p, c_p, c_int, c_int, c_f, c_f, c_p, c_p, c_p]),
     "msl_style_output": (c_int, [c_p] + [c_int] * 3 + [c_p, c_p, c_f, c_f, c_f, c_p]),
+    "msl_style_input_window": (c_int, [c_p, c_p] + [c_int] * 8 + [c_p, c_p, c_p, c_int, c_p]),
+    "msl_style_output_resampled": (c_int, [c_p] + [c_int] * 9 + [c_p] + [c_int] * 6 + [c_f, c_f, c_f, c_p]),
+    "msl_label_resize_nearest": (c_int, [c_p, c_int, c_int, c_p, c_int, c_int, c_p]),
+    "msl_predict_rectify": (c_int, [c_p, c_p, c_p] + [c_int] * 6 + [c_p, c_p, c_p, c_p]),
     "msl_launch_guard_probe": (c_int, [c_int, c_p, c_p]),
     "msl_pconv_dgrad_resmask_sc": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_p, c_p, c_sz, c_p, c_p,
                                            c_int]),

@@ -1320,6 +1320,37 @@ def predict_up(low, out_hw, low_flip=None, label=None, confusion=None, want_argm
     return arg
 
 
+def predict_rectify(low, crop0, crop1, out_hw, segy0, label=None, confusion=None, want_argmax=False):
+    """predict_up without flip followed by the reference's Trainer.rectification with both crops, one launch
+    (msl_predict_rectify): `crop0` / `crop1` are the low-resolution logits of the left and right half-size
+    windows, magnified, stylised and forwarded; inside rows [segy0, segy0 + ho/2) a crop's class replaces the
+    pixel's where its winning logit is strictly greater.  label / confusion / want_argmax as predict_up."""
+    low = _check_act(low.detach(), "predict_rectify")
+    c, hi, wi, ho, wo = _geom(low, out_hw)
+    crops = []
+    for t in (crop0, crop1):
+        t = _check_act(t.detach(), "predict_rectify")
+        if t.shape != low.shape:
+            raise hip.MSLError("predict_rectify: the crops' logits must have low's shape")
+        crops.append(t)
+    if (label is None) != (confusion is None):
+        raise hip.MSLError("predict_rectify: label and confusion go together")
+    if label is not None:
+        label = label.contiguous()
+        if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
+            raise hip.MSLError(f"predict_rectify: label must be a CUDA int64 tensor with {ho * wo} elements")
+        if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
+                not confusion.is_contiguous()):
+            raise hip.MSLError(f"predict_rectify: confusion must be a contiguous CUDA int64 tensor with {c * c} elements")
+    elif not want_argmax:
+        raise hip.MSLError("predict_rectify: nothing to compute (no label / confusion and want_argmax=False)")
+    arg = torch.empty(ho * wo, dtype=torch.int32, device=low.device) if want_argmax else None
+    hip.check(hip.load().msl_predict_rectify(low.data_ptr(), crops[0].data_ptr(), crops[1].data_ptr(), c, hi, wi, ho, wo,
+                                             int(segy0), hip.ptr(label), hip.ptr(confusion), hip.ptr(arg),
+                                             hip.stream_ptr()), "msl_predict_rectify")
+    return arg
+
+
 # the maps of predict_images: name -> trailing shape after (ho, wo)
 IMAGE_MAPS = {"class": (), "ids": (), "color": (3,), "confidence": (3,), "pseudo": ()}
 _IMAGE_TABLES = {}  # (num_classes, device) -> (id_lut [C], palette [C*3], shade [4*C*3]) uint8 on the device
@@ -1745,6 +1776,72 @@ def style_output(x, grid=False, rgb=True, seg=False, mean=(0.0, 0.0, 0.0)):
     hip.check(hip.load().msl_style_output(x.data_ptr(), int(bool(grid)), h, w, hip.ptr(u8), hip.ptr(sg), float(mean[0]),
                                           float(mean[1]), float(mean[2]), hip.stream_ptr()), "msl_style_output")
     return u8, sg
+
+
+def style_input_window(img, window, size, w1, b1, cpad=3):
+    """style_input of the window (x0, y0, cw, ch) of `img` magnified to size = (h, w) by torch's nearest rule
+    (F.interpolate's default): msl_style_input_window, one launch, the magnified image never written."""
+    if img.dtype == torch.uint8:
+        ok, ih, iw = img.dim() == 3 and img.size(2) == 3, img.size(0), img.size(1)
+    else:
+        ok, ih, iw = img.dtype == _f32 and img.dim() == 4 and tuple(img.shape[:2]) == (1, 3), img.size(-2), img.size(-1)
+    if not (ok and img.is_cuda):
+        raise hip.MSLError(f"style_input_window: expected a CUDA uint8 (H,W,3) or fp32 (1,3,H,W) image, got "
+                           f"{tuple(img.shape)} {img.dtype} {img.device}")
+    img, w1, b1 = img.contiguous(), w1.contiguous(), b1.contiguous()
+    if w1.numel() != 9 or b1.numel() != 3 or w1.dtype != _f32 or b1.dtype != _f32:
+        raise hip.MSLError("style_input_window: the 1x1 conv needs a (3,3,1,1) weight and a (3,) bias in fp32")
+    x0, y0, cw, ch = (int(v) for v in window)
+    h, w = int(size[0]), int(size[1])
+    if h < 1 or w < 1:
+        raise hip.MSLError(f"style_input_window: size {size}")
+    y = torch.empty((1, cpad, h + 2, w + 2), dtype=_f32, device=img.device)
+    u8 = img.dtype == torch.uint8
+    hip.check(hip.load().msl_style_input_window(img.data_ptr() if u8 else None, None if u8 else img.data_ptr(), ih, iw,
+                                                x0, y0, cw, ch, h, w, w1.data_ptr(), b1.data_ptr(), y.data_ptr(), cpad,
+                                                hip.stream_ptr()), "msl_style_input_window")
+    return y
+
+
+def style_output_resampled(x, out, window=None, grid=False, mid=None, full=None, off=(0, 0), mean=(0.0, 0.0, 0.0)):
+    """style_output's seg tensor of the 3-channel map x, gathered by torch's nearest rule into the window
+    (dx0, dy0, dw, dh) of `out` (1, 3, Hd, Wd), in place: msl_style_output_resampled.  One map (full None): the
+    window is x resized to (dh, dw).  Two maps: x resized to mid = (mh, mw) sits at off = (oy, ox) of a
+    stitched map of full = (fh, fw), which is resized to (Hd, Wd); only the cells of the window whose
+    source is this image's part are written.  `window` defaults to the whole of `out`."""
+    x, c, h, w = _style_src(x, grid, "style_output_resampled")
+    if c != 3:
+        raise hip.MSLError(f"style_output_resampled: expected 3 channels, got {c}")
+    if not (out.is_cuda and out.dtype == _f32 and out.dim() == 4 and tuple(out.shape[:2]) == (1, 3) and
+            out.is_contiguous() and out.device == x.device):
+        raise hip.MSLError(f"style_output_resampled: out must be a contiguous CUDA fp32 (1,3,H,W) tensor, got "
+                           f"{tuple(out.shape)} {out.dtype}")
+    hd, wd = out.size(2), out.size(3)
+    dx0, dy0, dw, dh = (0, 0, wd, hd) if window is None else (int(v) for v in window)
+    if full is None:
+        mh, mw, fh, fw = dh, dw, 0, 0
+    else:
+        (mh, mw), (fh, fw) = (int(v) for v in mid), (int(v) for v in full)
+    hip.check(hip.load().msl_style_output_resampled(x.data_ptr(), int(bool(grid)), h, w, mh, mw, fh, fw, int(off[0]),
+                                                    int(off[1]), out.data_ptr(), hd, wd, dx0, dy0, dw, dh,
+                                                    float(mean[0]), float(mean[1]), float(mean[2]), hip.stream_ptr()),
+              "msl_style_output_resampled")
+    return out
+
+
+def label_resize_nearest(label, size):
+    """An int64 (H, W) label map resized to size = (ho, wo) by torch's nearest rule: msl_label_resize_nearest."""
+    if not (label.is_cuda and label.dtype == torch.int64 and label.dim() == 2):
+        raise hip.MSLError(f"label_resize_nearest: expected a CUDA int64 (H,W) map, got {tuple(label.shape)} "
+                           f"{label.dtype} {label.device}")
+    label = label.contiguous()
+    ho, wo = int(size[0]), int(size[1])
+    if ho < 1 or wo < 1:
+        raise hip.MSLError(f"label_resize_nearest: size {size}")
+    out = torch.empty((ho, wo), dtype=torch.int64, device=label.device)
+    hip.check(hip.load().msl_label_resize_nearest(label.data_ptr(), label.size(0), label.size(1), out.data_ptr(), ho, wo,
+                                                  hip.stream_ptr()), "msl_label_resize_nearest")
+    return out
 
 
 def conv3x3_reflect(x_grid, weight, bias, cache):

@@ -130,12 +130,16 @@ class StyleNet:
         return calls
 
     # ------------------------------------------------------------------ the pass
-    def encode(self, img):
+    def encode(self, img, window=None, size=None):
         """relu4_1's conv output (before its ReLU) as a grid (1, 512, h+2, w+2) whose interior is valid, from
-        a uint8 (H, W, 3) RGB image or a float (1, 3, H, W) tensor in [0, 1] on the device."""
+        a uint8 (H, W, 3) RGB image or a float (1, 3, H, W) tensor in [0, 1] on the device.  With `window`
+        (x0, y0, cw, ch) and `size` (h, w): of that window of the image magnified to h x w by torch's nearest
+        rule (ops.style_input_window: the reference's F.interpolate(crop, size) ahead of the network)."""
         y = None
         for i, st in enumerate(self.enc_stages):
-            if i == 0:
+            if i == 0 and window is not None:
+                g = ops.style_input_window(img, window, size, self.w1, self.b1, cpad=st.cin)
+            elif i == 0:
                 g = ops.style_input(img, self.w1, self.b1, cpad=st.cin)
             else:
                 g = ops.style_pad(y, grid=True, act=st.act, resample=st.resample)
@@ -164,9 +168,10 @@ class StyleNet:
             y = ops.conv3x3_reflect(g, st.weight, st.bias, st.cache)
         return y
 
-    def stylize(self, content, style_stats, alpha=1.0, weights=None):
-        """The stylised image as the decoder's last grid (see decode): `content` as encode() takes it,
-        `style_stats` from encode_style, `weights` the interpolation weights of several styles."""
+    def stylize(self, content, style_stats, alpha=1.0, weights=None, window=None, size=None):
+        """The stylised image as the decoder's last grid (see decode): `content` (and `window`, `size`) as
+        encode() takes it, `style_stats` from encode_style, `weights` the interpolation weights of several
+        styles."""
         if weights is None:
             if style_stats.size(0) != 1:
                 raise ValueError("several styles need interpolation weights")
@@ -175,6 +180,6 @@ class StyleNet:
             raise ValueError(f"{len(weights)} interpolation weights for {style_stats.size(0)} styles")
         if not 0.0 <= alpha <= 1.0:
             raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
-        feat = self.encode(content)
+        feat = self.encode(content, window, size)
         a, b = ops.style_adain_coef(ops.style_stats(feat, grid=True, relu=True), style_stats, weights, alpha)
         return self.decode(feat, a, b)

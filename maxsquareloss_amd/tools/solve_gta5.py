@@ -17,8 +17,8 @@ same sums, added inside the weight-gradient GEMMs instead of by a second pass.
 
 The losses run fused from the low-resolution logits (utils/loss.py), so the
 two softmax tensors of the reference (:182-183) are never materialised.
-Style-transfer augmentation (exp_tag source_aug/target_aug) is out of scope
-(SURVEY.md §2, §8f).
+Style transfer inside the loop is tools/ADAIN.py, which subclasses this trainer
+(DESIGN.md §3.14).
 
 Data: with --source_data_path and --target_data_path the source (GTA5) and target
 (Cityscapes) items come from files (datasets/: Pillow decodes on --data_loader_workers

@@ -83,6 +83,21 @@ class Eval:
         else:
             ops.predict_up(low, out_hw, low_flip, gt, self._dev)
 
+    def add_batch_rectified(self, gt_image, low, crop0, crop1, out_hw, segy0):
+        """add_batch_low without flip, followed by the reference's Trainer.rectification with the logits of
+        its two stylised, magnified crops, in the same launch (ops.predict_rectify)."""
+        if not (torch.is_tensor(low) and low.is_cuda and low.dim() == 4 and low.size(0) == 1):
+            raise hip.MSLError("Eval.add_batch_rectified: expects device logits [1, C, hi, wi]")
+        c = low.size(1)
+        if c != self.num_class:
+            raise hip.MSLError(f"Eval.add_batch_rectified: {c} classes, Eval built for {self.num_class}")
+        gt = gt_image.to(device=low.device, dtype=torch.int64).reshape(-1).contiguous()
+        if gt.numel() != int(out_hw[0]) * int(out_hw[1]):
+            raise hip.MSLError("Eval.add_batch_rectified: label and prediction sizes differ")
+        if self._dev is None or self._dev.device != low.device:
+            self._dev = torch.zeros(c * c, dtype=torch.int64, device=low.device)
+        ops.predict_rectify(low, crop0, crop1, out_hw, segy0, gt, self._dev)
+
     def reset(self):
         self._host = np.zeros((self.num_class,) * 2)
         if self._dev is not None:
