@@ -7,7 +7,9 @@ reference only runs bs=1: IW_MaxSquareloss broadcasts (N,H,W) weights against
 image PAIR (1, C, 2, H, W): the source and target images of one UDA iteration laid
 out [C][2][H][W], each image convolved, pooled and batch-normalised on its own (its
 own bs=1 statistics) while every conv GEMM runs once over both (pair_join /
-pair_split; the trunk ops take either form, the losses one image).
+pair_split; the trunk ops take either form, the losses one image).  The host sequences several
+Functions share live once: next to _conv_call for the convs (_pconv_fwd, _pconv_dgrad, _wgrad_call,
+_pconv_wgrad, _stack_bias / _branch_grads), in _LossUp and its _UP_LOSSES table for the fused losses.
 """
 import ctypes
 from contextlib import nullcontext as _nullctx
@@ -41,7 +43,6 @@ def set_conv_math(math):
 # each operand tensor scaled by a power of two and split into two fp16 terms, three products per
 # slice on v_mfma_f32_32x32x16_f16 with fp32 sums (fp32-accurate; dconv_kernels.h Split2h).
 F32_FORMS = {"mfma_f32": 0, "bf16x6": 2, "f16x3": 5}
-SPLIT_FORMS = ("bf16x6", "f16x3")  # the forms the HIP pointwise / 128-row kernels run split
 
 
 def _form_code():
@@ -65,10 +66,6 @@ def set_bn_fused(fused):
 
 def f32_form():
     return {v: k for k, v in F32_FORMS.items()}[hip.FORMS.f32_form]
-
-
-def _fn(lib, name, math):
-    return getattr(lib, name + "_bf16") if math == "bf16" else getattr(lib, name)
 
 
 def _h3(math="fp32"):
@@ -122,6 +119,76 @@ def _split_gemm(m, k_other):
     image operand (128-row tiles: M > 64), or a weight gradient of these channel counts the pre-split
     kernel (both >= 128): a partials launch only pays off where one of them reads the tensor."""
     return m > 64 or min(m, k_other) >= 128
+
+
+def _pconv_fwd(lib, math, x, packed, y, cin, cout, p, scale_from=None):
+    """y = W x on the pointwise forward GEMM of this math.  Returns x's absmax partials (_parts), which
+    the weight gradient reads again; `scale_from`: a tensor with x's absmax whose partials serve instead."""
+    wsb = lib.msl_pconv_fwd_workspace(cin, cout, p)
+    ws = hip.workspace(wsb, x.device)
+    if scale_from is not None:
+        xpart = _parts(scale_from, math)
+    else:
+        xpart = _parts(x, math, compute=_split_gemm(cout, cin))
+    hip.check(_conv_call(lib, "msl_pconv_fwd", math,
+                         (x.data_ptr(), packed.data_ptr(), y.data_ptr(), cin, cout, p,
+                          hip.forms(), ws.data_ptr(), wsb, hip.stream_ptr()), (xpart,)), "msl_pconv_fwd")
+    return xpart
+
+
+def _pconv_dgrad(lib, math, gy, packed_d, dx, cin, cout, p, acc, fm, ws, wsb, gpart):
+    """dx = W^T dy, or dx += W^T dy with `acc`, on the pointwise data-gradient GEMM of this math and of
+    the forward's forms `fm`, in the caller's workspace (msl_pconv_dgrad_workspace).  The bf16 entry
+    point has no accumulate epilogue: it ignores `acc`."""
+    head = (gy.data_ptr(), packed_d.data_ptr(), dx.data_ptr(), cin, cout, p)
+    tail = (ctypes.addressof(fm), ws.data_ptr(), wsb, hip.stream_ptr())
+    if math == "bf16":
+        st = lib.msl_pconv_dgrad_bf16(*head, *tail)
+    else:
+        fn = lib.msl_pconv_dgrad_f16 if math == "fp16" else lib.msl_pconv_dgrad_acc_sc
+        st = fn(*head, acc, *tail, *_pp(gpart))
+    hip.check(st, "msl_pconv_dgrad")
+
+
+def _wgrad_call(lib, name, math, args, wsb, fm, operands, parts, sink=None):
+    """The weight-gradient GEMM `name`(*args, fm, workspace, stream).  With a `sink` (grad_sink: the
+    GEMM accumulates into the flat gradient buffer) it runs on the side stream under ASYNC_WGRAD, its
+    workspace allocated there and its operands kept for that stream, and the flat buffer is notified."""
+    dev = operands[0].device
+    side = _wgrad_stream(operands[0]) if (ASYNC_WGRAD and sink is not None) else None
+    with torch.cuda.stream(side) if side is not None else _nullctx():
+        ws = hip.workspace(wsb, dev)
+        hip.check(_conv_call(lib, name, math,
+                             (*args, ctypes.addressof(fm), ws.data_ptr(), wsb, hip.stream_ptr()), parts), name)
+    if side is not None:
+        _keep(side, *operands, *(q[0] for q in parts if q is not None))
+    if sink is not None:
+        sink[1].notify(sink[2])
+
+
+def _pconv_wgrad(lib, math, x, gy, xpart, gpart, cin, cout, p, weight, fm):
+    """dW = dy x^T on the pointwise weight-gradient GEMM: accumulated into `weight`'s slice of the flat
+    gradient buffer when it has a sink (returns None: autograd gets no gradient), else a new tensor."""
+    sink = grad_sink(weight)
+    dst = sink[0] if sink is not None else torch.empty_like(weight)
+    _wgrad_call(lib, "msl_pconv_wgrad", math,
+                (x.data_ptr(), gy.data_ptr(), dst.data_ptr(), cin, cout, p, int(sink is not None)),
+                lib.msl_pconv_wgrad_workspace(cin, cout, p), fm, (x, gy), (xpart, gpart), sink)
+    return None if sink is not None else dst
+
+
+def _stack_bias(b0, b1, nb):
+    """The biases of a one- or two-branch conv as one [nb][cout] tensor; None without biases."""
+    if b0 is None:
+        return None
+    return torch.stack([b0] if nb == 1 else [b0, b1]).contiguous()
+
+
+def _branch_grads(dw_all, db_all, nb):
+    """(dw0, dw1, db0, db1) for autograd from the stacked [nb][...] gradients (None: not computed)."""
+    def pair(t):
+        return (None, None) if t is None else (t[0], t[1] if nb > 1 else None)
+    return pair(dw_all) + pair(db_all)
 
 
 def _check_act(x, name, images=False):
@@ -384,9 +451,7 @@ class _DConv3x3(Function):
         h, w = x.shape[-2], x.shape[-1]
         lib = hip.load()
         packed = cache.get(weights, cin, cout, 0)
-        bias = None
-        if b0 is not None:
-            bias = torch.stack([b0] if nb == 1 else [b0, b1]).contiguous()
+        bias = _stack_bias(b0, b1, nb)
         y = _like(x, cout, h, w)
         wsb = lib.msl_dconv_fwd_workspace(nb, cin, cout, h, w, n)
         ws = hip.workspace(wsb, x.device)
@@ -432,28 +497,19 @@ class _DConv3x3(Function):
         sink = grad_sink(weights[0]) if (nb == 1 and not has_bias and ctx.needs_input_grad[1]) else None
         wsb = lib.msl_dconv_wgrad_workspace(nb, cin, cout, h, w, n)
         if sink is not None:
-            g, fg, i = sink
-            side = _wgrad_stream(x) if ASYNC_WGRAD else None
-            with torch.cuda.stream(side) if side is not None else _nullctx():
-                ws = hip.workspace(wsb, x.device)
-                hip.check(_conv_call(lib, "msl_dconv_wgrad", math,
-                                     (x.data_ptr(), gy.data_ptr(), g.data_ptr(), None, 1, cin, cout, h, w, n, dil0, 0, 1,
-                                      ctypes.addressof(ctx.fm), ws.data_ptr(), wsb, hip.stream_ptr()), (xpart, gpart)), "msl_dconv_wgrad")
-            if side is not None:
-                _keep(side, x, gy, *(q[0] for q in (xpart, gpart) if q is not None))
-            fg.notify(i)
+            _wgrad_call(lib, "msl_dconv_wgrad", math,
+                        (x.data_ptr(), gy.data_ptr(), sink[0].data_ptr(), None, 1, cin, cout, h, w, n, dil0, 0, 1),
+                        wsb, ctx.fm, (x, gy), (xpart, gpart), sink)
             return dx, None, None, None, None, None, None, None
+        # without a sink the workspace comes before the gradient tensors: not _wgrad_call's order
         ws = hip.workspace(wsb, x.device)
         dw_all = torch.empty((nb, cout, cin, 3, 3), dtype=_f32, device=x.device)
         db_all = torch.empty((nb, cout), dtype=_f32, device=x.device) if has_bias else None
         hip.check(_conv_call(lib, "msl_dconv_wgrad", math,
                              (x.data_ptr(), gy.data_ptr(), dw_all.data_ptr(), hip.ptr(db_all), nb, cin, cout, h, w,
-                              n, dil0, d1, 0, ctypes.addressof(ctx.fm), ws.data_ptr(), wsb, s), (xpart, gpart)), "msl_dconv_wgrad")
-        dw0 = dw_all[0]
-        dw1 = dw_all[1] if nb > 1 else None
-        db0 = db_all[0] if has_bias else None
-        db1 = db_all[1] if (has_bias and nb > 1) else None
-        return dx, dw0, dw1, db0, db1, None, None, None
+                              n, dil0, d1, 0, ctypes.addressof(ctx.fm), ws.data_ptr(), wsb, s), (xpart, gpart)),
+                  "msl_dconv_wgrad")
+        return (dx, *_branch_grads(dw_all, db_all, nb), None, None, None)
 
 
 def dconv3x3(x, weight, dilation, cache):
@@ -523,20 +579,12 @@ class _ASPPShift(Function):
         sp = cache.shift_pack()
         packed = sp.get(weights, cin, c, 0)
         z = torch.empty((1, m, p), dtype=_f32, device=x.device)
-        wsb = lib.msl_pconv_fwd_workspace(cin, m, p)
-        ws = hip.workspace(wsb, x.device)
         math = CONV_MATH
-        xpart = _parts(x, math, compute=_split_gemm(m, cin))
-        s = hip.stream_ptr()
-        hip.check(_conv_call(lib, "msl_pconv_fwd", math,
-                             (x.data_ptr(), packed.data_ptr(), z.data_ptr(), cin, m, p,
-                              hip.forms(), ws.data_ptr(), wsb, s), (xpart,)), "msl_pconv_fwd")
-        bias = None
-        if b0 is not None:
-            bias = torch.stack([b0] if nb == 1 else [b0, b1]).contiguous()
+        xpart = _pconv_fwd(lib, math, x, packed, z, cin, m, p)
+        bias = _stack_bias(b0, b1, nb)
         y = _like(x, c, h, w)
         hip.check(lib.msl_aspp_shift_add(z.data_ptr(), hip.ptr(bias), y.data_ptr(), nb, c, h, w, n, dil0,
-                                         dil1 if nb > 1 else 0, s), "msl_aspp_shift_add")
+                                         dil1 if nb > 1 else 0, hip.stream_ptr()), "msl_aspp_shift_add")
         ctx.save_for_backward(x, *weights)
         ctx.meta = (nb, cin, c, h, w, n, dil0, dil1, b0 is not None, cache, math)
         ctx.xpart = xpart
@@ -562,30 +610,16 @@ class _ASPPShift(Function):
             dx = torch.empty_like(x)
             wsb = lib.msl_pconv_dgrad_workspace(cin, m, p)
             ws = hip.workspace(wsb, x.device)
-            cnt = ctypes.addressof(ctx.fm)
-            if math == "bf16":
-                st = lib.msl_pconv_dgrad_bf16(g.data_ptr(), packed_d.data_ptr(), dx.data_ptr(), cin, m, p, cnt,
-                                              ws.data_ptr(), wsb, s)
-            else:
-                fn = lib.msl_pconv_dgrad_f16 if math == "fp16" else lib.msl_pconv_dgrad_acc_sc
-                st = fn(g.data_ptr(), packed_d.data_ptr(), dx.data_ptr(), cin, m, p, 0, cnt, ws.data_ptr(), wsb, s,
-                        *_pp(gpart))
-            hip.check(st, "msl_pconv_dgrad")
-        dw0 = dw1 = None
+            _pconv_dgrad(lib, math, g, packed_d, dx, cin, m, p, 0, ctx.fm, ws, wsb, gpart)
+        dw_all = None
         if any(ctx.needs_input_grad[1:3]):
-            dwp = torch.empty((m, cin), dtype=_f32, device=x.device)
-            wsb = lib.msl_pconv_wgrad_workspace(cin, m, p)
-            ws = hip.workspace(wsb, x.device)
-            hip.check(_conv_call(lib, "msl_pconv_wgrad", math,
-                                 (x.data_ptr(), g.data_ptr(), dwp.data_ptr(), cin, m, p, 0, ctypes.addressof(ctx.fm), ws.data_ptr(), wsb, s),
-                                 (ctx.xpart, gpart)), "msl_pconv_wgrad")
+            dwp = torch.empty((m, cin), dtype=_f32, device=x.device)  # dW', never a parameter's: no sink
+            _wgrad_call(lib, "msl_pconv_wgrad", math, (x.data_ptr(), g.data_ptr(), dwp.data_ptr(), cin, m, p, 0),
+                        lib.msl_pconv_wgrad_workspace(cin, m, p), ctx.fm, (x, g), (ctx.xpart, gpart))
             dw_all = torch.empty((nb, c, cin, 3, 3), dtype=_f32, device=x.device)
-            hip.check(lib.msl_aspp_weight_grad(dwp.data_ptr(), nb, c, cin, dw_all.data_ptr(), s), "msl_aspp_weight_grad")
-            dw0 = dw_all[0]
-            dw1 = dw_all[1] if nb > 1 else None
-        db0 = db_all[0] if has_bias else None
-        db1 = db_all[1] if (has_bias and nb > 1) else None
-        return dx, dw0, dw1, db0, db1, None, None, None
+            hip.check(lib.msl_aspp_weight_grad(dwp.data_ptr(), nb, c, cin, dw_all.data_ptr(), s),
+                      "msl_aspp_weight_grad")
+        return (dx, *_branch_grads(dw_all, db_all, nb), None, None, None)
 
 
 def aspp2(x, w0, b0, w1, b1, dil0, dil1, cache):
@@ -617,15 +651,9 @@ class _PConv(Function):
         lib = hip.load()
         packed = cache.get([weight], cin, cout, 0)
         y = _like(x, cout, h, w)
-        wsb = lib.msl_pconv_fwd_workspace(cin, cout, p)
-        ws = hip.workspace(wsb, x.device)
         math = CONV_MATH
         # f16x3: x's absmax partials once for the forward and the weight gradient
-        xpart = _parts(x, math, compute=_split_gemm(cout, cin))
-        hip.check(_conv_call(lib, "msl_pconv_fwd", math,
-                             (x.data_ptr(), packed.data_ptr(), y.data_ptr(), cin, cout, p,
-                              hip.forms(), ws.data_ptr(), wsb, hip.stream_ptr()), (xpart,)),
-                  "msl_pconv_fwd")
+        xpart = _pconv_fwd(lib, math, x, packed, y, cin, cout, p)
         ctx.save_for_backward(x, weight)
         ctx.meta = (cin, cout, p, cache, math)
         ctx.xpart = xpart
@@ -664,22 +692,17 @@ class _PConv(Function):
             packed_d = cache.get([weight], cin, cout, 1)
             wsb = lib.msl_pconv_dgrad_workspace(cin, cout, p)
             ws = hip.workspace(wsb, x.device)
-            cnt = ctypes.addressof(ctx.fm)
-            if math == "bf16":
-                tgt = torch.empty_like(x) if acc else dx
-                hip.check(lib.msl_pconv_dgrad_bf16(gy.data_ptr(), packed_d.data_ptr(), tgt.data_ptr(), cin, cout, p,
-                                                   cnt, ws.data_ptr(), wsb, s), "msl_pconv_dgrad")
-                if acc:  # the bf16 form has no accumulate epilogue
-                    dx.add_(tgt)
-            elif res is not None:  # r06: dx = mask(dy of bn3) + W^T dy, the mask applied in the epilogue
+            if res is not None:  # r06: dx = mask(dy of bn3) + W^T dy, the mask applied in the epilogue
                 fn = lib.msl_pconv_dgrad_resmask_f16 if math == "fp16" else lib.msl_pconv_dgrad_resmask_sc
                 hip.check(fn(gy.data_ptr(), packed_d.data_ptr(), dx.data_ptr(), cin, cout, p, res.dy.data_ptr(),
-                             res.bits.data_ptr(), res.nimg, cnt, ws.data_ptr(), wsb, s, *_pp(gpart)),
-                          "msl_pconv_dgrad_resmask")
+                             res.bits.data_ptr(), res.nimg, ctypes.addressof(ctx.fm), ws.data_ptr(), wsb, s,
+                             *_pp(gpart)), "msl_pconv_dgrad_resmask")
+            elif math == "bf16" and acc:  # the bf16 form has no accumulate epilogue
+                tgt = torch.empty_like(x)
+                _pconv_dgrad(lib, math, gy, packed_d, tgt, cin, cout, p, 0, ctx.fm, ws, wsb, gpart)
+                dx.add_(tgt)
             else:
-                fn = lib.msl_pconv_dgrad_f16 if math == "fp16" else lib.msl_pconv_dgrad_acc_sc
-                hip.check(fn(gy.data_ptr(), packed_d.data_ptr(), dx.data_ptr(), cin, cout, p, acc, cnt,
-                             ws.data_ptr(), wsb, s, *_pp(gpart)), "msl_pconv_dgrad")
+                _pconv_dgrad(lib, math, gy, packed_d, dx, cin, cout, p, acc, ctx.fm, ws, wsb, gpart)
         # a downsample conv (r05): its data gradient goes to the ResidualGrad that the block's conv1 sums
         # into its own (msl_pconv_dgrad_acc) - unless conv1's backward already ran, then autograd adds it
         to = ctx.grad_to
@@ -687,21 +710,8 @@ class _PConv(Function):
             to.g, dx = dx, None
         if not ctx.needs_input_grad[1]:
             return dx, None, None, None, None
-        sink = grad_sink(weight)
-        dst = sink[0] if sink is not None else torch.empty_like(weight)
-        wsb = lib.msl_pconv_wgrad_workspace(cin, cout, p)
-        side = _wgrad_stream(x) if (ASYNC_WGRAD and sink is not None) else None
-        with torch.cuda.stream(side) if side is not None else _nullctx():
-            ws = hip.workspace(wsb, x.device)
-            hip.check(_conv_call(lib, "msl_pconv_wgrad", math,
-                                 (x.data_ptr(), gy.data_ptr(), dst.data_ptr(), cin, cout, p, int(sink is not None),
-                                  ctypes.addressof(ctx.fm), ws.data_ptr(), wsb, hip.stream_ptr()), (ctx.xpart, gpart)), "msl_pconv_wgrad")
-        if side is not None:
-            _keep(side, x, gy, *(q[0] for q in (ctx.xpart, gpart) if q is not None))
-        if sink is None:
-            return dx, dst, None, None, None
-        sink[1].notify(sink[2])
-        return dx, None, None, None, None
+        dw = _pconv_wgrad(lib, math, x, gy, ctx.xpart, gpart, cin, cout, p, weight, ctx.fm)
+        return dx, dw, None, None, None
 
 
 def pconv(x, weight, cache, residual_grad=None, grad_to=None):
@@ -783,8 +793,6 @@ class _StemConv(Function):
         wmat = weight.detach().contiguous()
         packed = cache.get([wmat], kk, cout, 0)
         y = _like(x, cout, ho, wo)
-        wsb = lib.msl_pconv_fwd_workspace(kk, cout, p)
-        ws = hip.workspace(wsb, x.device)
         # the bf16 / fp16 conv maths keep the stem (the raw image, values ~1e2; 2.5 GFLOP per image) in
         # the fp32 form: 8 significant bits there cost 3-4 % of the target loss after one update
         math = "fp32" if CONV_MATH in ("bf16", "fp16") else CONV_MATH
@@ -795,10 +803,7 @@ class _StemConv(Function):
         # the same bits either way; the stem's weight gradient (64 x 147, exact-f32 tiles) reads none.
         cover = (stride <= min(kh, kw) and pad < min(kh, kw) and (ho - 1) * stride - pad + kh >= h and
                  (wo - 1) * stride - pad + kw >= w)
-        cpart = _parts(x, math) if cover else _parts(col, math, compute=_split_gemm(cout, kk))
-        hip.check(_conv_call(lib, "msl_pconv_fwd", math,
-                             (col.data_ptr(), packed.data_ptr(), y.data_ptr(), kk, cout, p,
-                              hip.forms(), ws.data_ptr(), wsb, s), (cpart,)), "msl_pconv_fwd")
+        cpart = _pconv_fwd(lib, math, col, packed, y, kk, cout, p, scale_from=x if cover else None)
         ctx.save_for_backward(col, weight)
         ctx.meta = (cin, h, w, n, kh, kw, stride, pad, ho, wo, cache, math)
         ctx.cpart = cpart
@@ -819,35 +824,14 @@ class _StemConv(Function):
             dcol = torch.empty_like(col)
             wsb = lib.msl_pconv_dgrad_workspace(kk, cout, p)
             ws = hip.workspace(wsb, gy.device)
-            cnt = ctypes.addressof(ctx.fm)
-            if math == "bf16":
-                st = lib.msl_pconv_dgrad_bf16(gy.data_ptr(), packed_d.data_ptr(), dcol.data_ptr(), kk, cout, p, cnt,
-                                              ws.data_ptr(), wsb, s)
-            else:
-                fn = lib.msl_pconv_dgrad_f16 if math == "fp16" else lib.msl_pconv_dgrad_acc_sc
-                st = fn(gy.data_ptr(), packed_d.data_ptr(), dcol.data_ptr(), kk, cout, p, 0, cnt, ws.data_ptr(), wsb,
-                        s, *_pp(gpart))
-            hip.check(st, "msl_pconv_dgrad")
+            _pconv_dgrad(lib, math, gy, packed_d, dcol, kk, cout, p, 0, ctx.fm, ws, wsb, gpart)
             dx = _like(col, cin, h, w)
             hip.check(lib.msl_col2im(dcol.data_ptr(), cin, h, w, n, kh, kw, stride, pad, 1, ho, wo, dx.data_ptr(), s),
                       "msl_col2im")
         if not ctx.needs_input_grad[1]:
             return dx, None, None, None, None
-        sink = grad_sink(weight)
-        dst = sink[0] if sink is not None else torch.empty_like(weight)
-        wsb = lib.msl_pconv_wgrad_workspace(kk, cout, p)
-        side = _wgrad_stream(gy) if (ASYNC_WGRAD and sink is not None) else None
-        with torch.cuda.stream(side) if side is not None else _nullctx():
-            ws = hip.workspace(wsb, gy.device)
-            hip.check(_conv_call(lib, "msl_pconv_wgrad", math,
-                                 (col.data_ptr(), gy.data_ptr(), dst.data_ptr(), kk, cout, p, int(sink is not None),
-                                  ctypes.addressof(ctx.fm), ws.data_ptr(), wsb, hip.stream_ptr()), (ctx.cpart, gpart)), "msl_pconv_wgrad")
-        if side is not None:
-            _keep(side, col, gy, *(q[0] for q in (ctx.cpart, gpart) if q is not None))
-        if sink is None:
-            return dx, dst, None, None, None
-        sink[1].notify(sink[2])
-        return dx, None, None, None, None
+        dw = _pconv_wgrad(lib, math, col, gy, ctx.cpart, gpart, kk, cout, p, weight, ctx.fm)
+        return dx, dw, None, None, None
 
 
 def stem_conv(x, weight, stride, pad, cache):
@@ -974,235 +958,72 @@ def _geom(low, out_hw):
     return c, hi, wi, int(out_hw[0]), int(out_hw[1])
 
 
-class _CEUp(Function):
+def _iw_outputs(c, device):
+    """(hist int32[C], weights fp32[C]): the importance-weighted losses' extra outputs."""
+    return torch.empty(c, dtype=torch.int32, device=device), torch.empty(c, dtype=_f32, device=device)
+
+
+# The fused upsample-loss kinds: kind -> (second operand: None, "labels" or "low2"; the float argument
+# after the geometry or None; whether the backward takes that float too; whether the forward also
+# writes the IW histogram and class weights).  The entry points are msl_<kind>_up_fwd / _bwd:
+#   fwd(low, [operand], c, hi, wi, ho, wo, [float], out, stats, [hist, weights], ws, wsb, stream)
+#   bwd(low, [operand], c, hi, wi, ho, wo, [float], stats, g, d, ws, wsb, stream)
+_UP_LOSSES = {
+    "ce": ("labels", None, False, False),
+    "maxsquare": (None, None, False, False),
+    "iw_maxsquare": (None, "ratio", False, True),
+    "multi_ce": ("low2", "thr", True, False),
+    "entropy": (None, None, False, False),
+    "iw_entropy": (None, "ratio", False, True),
+    "hard_ce": (None, "thr", True, False),
+}
+
+
+class _LossUp(Function):
+    """A loss of the upsampled logits computed from the low-resolution ones, by `kind` (_UP_LOSSES)."""
+
     @staticmethod
-    def forward(ctx, low, labels, ho, wo):
-        low = _check_act(low, "ce_up")
-        labels = labels.contiguous()
-        c, hi, wi, ho, wo = _geom(low, (ho, wo))
-        if labels.dtype != torch.int64 or labels.numel() != ho * wo:
-            raise hip.MSLError(f"ce_up: labels must be int64 with {ho*wo} elements")
+    def forward(ctx, kind, low, other, ho, wo, val):
+        operand, fname, val_bwd, iw = _UP_LOSSES[kind]
+        low = _check_act(low, kind + "_up")
+        if operand == "low2":
+            other = _check_act(other.detach(), kind + "_up")
+        elif operand == "labels":
+            other = other.contiguous()
+        c, hi, wi, ho, wo = geo = _geom(low, (ho, wo))
+        if operand == "labels" and (other.dtype != torch.int64 or other.numel() != ho * wo):
+            raise hip.MSLError(f"{kind}_up: labels must be int64 with {ho*wo} elements")
         lib = hip.load()
         out = torch.empty((), dtype=_f32, device=low.device)
         st = _stats(low.device)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+        extra = _iw_outputs(c, low.device) if iw else ()
+        wsb = lib.msl_loss_workspace(*geo)
         ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_ce_up_fwd(low.data_ptr(), labels.data_ptr(), c, hi, wi, ho, wo, out.data_ptr(),
-                                    st.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()), "msl_ce_up_fwd")
-        ctx.save_for_backward(low, labels, st)
-        ctx.geo = (c, hi, wi, ho, wo)
-        return out
+        head = (low.data_ptr(),) if operand is None else (low.data_ptr(), other.data_ptr())
+        fval = () if fname is None else (float(val),)
+        name = f"msl_{kind}_up_fwd"
+        hip.check(getattr(lib, name)(*head, *geo, *fval, out.data_ptr(), st.data_ptr(),
+                                     *(t.data_ptr() for t in extra), ws.data_ptr(), wsb, hip.stream_ptr()), name)
+        ctx.save_for_backward(*((low, st) if operand is None else (low, other, st)))
+        ctx.call = (kind, geo + (fval if val_bwd else ()))
+        if not iw:
+            return out
+        ctx.mark_non_differentiable(*extra)
+        return (out, *extra)
 
     @staticmethod
-    def backward(ctx, g):
-        low, labels, st = ctx.saved_tensors
-        c, hi, wi, ho, wo = ctx.geo
+    def backward(ctx, g, *_unused):
+        *head, st = ctx.saved_tensors
+        kind, geo = ctx.call
         lib = hip.load()
         g = g.to(_f32).contiguous()
-        d = torch.empty_like(low)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_ce_up_bwd(low.data_ptr(), labels.data_ptr(), c, hi, wi, ho, wo, st.data_ptr(),
-                                    g.data_ptr(), d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_ce_up_bwd")
-        return d, None, None, None
-
-
-class _MaxSquareUp(Function):
-    @staticmethod
-    def forward(ctx, low, ho, wo):
-        low = _check_act(low, "maxsquare_up")
-        c, hi, wi, ho, wo = _geom(low, (ho, wo))
-        lib = hip.load()
-        out = torch.empty((), dtype=_f32, device=low.device)
-        st = _stats(low.device)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_maxsquare_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, out.data_ptr(), st.data_ptr(),
-                                           ws.data_ptr(), wsb, hip.stream_ptr()), "msl_maxsquare_up_fwd")
-        ctx.save_for_backward(low, st)
-        ctx.geo = (c, hi, wi, ho, wo)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        low, st = ctx.saved_tensors
-        c, hi, wi, ho, wo = ctx.geo
-        lib = hip.load()
-        g = g.to(_f32).contiguous()
-        d = torch.empty_like(low)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_maxsquare_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, st.data_ptr(), g.data_ptr(),
-                                           d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_maxsquare_up_bwd")
-        return d, None, None
-
-
-class _IWMaxSquareUp(Function):
-    @staticmethod
-    def forward(ctx, low, ho, wo, ratio):
-        low = _check_act(low, "iw_maxsquare_up")
-        c, hi, wi, ho, wo = _geom(low, (ho, wo))
-        lib = hip.load()
-        out = torch.empty((), dtype=_f32, device=low.device)
-        st = _stats(low.device)
-        hist = torch.empty(c, dtype=torch.int32, device=low.device)
-        weights = torch.empty(c, dtype=_f32, device=low.device)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_iw_maxsquare_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, float(ratio), out.data_ptr(),
-                                              st.data_ptr(), hist.data_ptr(), weights.data_ptr(), ws.data_ptr(),
-                                              wsb, hip.stream_ptr()), "msl_iw_maxsquare_up_fwd")
-        ctx.save_for_backward(low, st)
-        ctx.geo = (c, hi, wi, ho, wo)
-        ctx.mark_non_differentiable(hist, weights)
-        return out, hist, weights
-
-    @staticmethod
-    def backward(ctx, g, _gh, _gw):
-        low, st = ctx.saved_tensors
-        c, hi, wi, ho, wo = ctx.geo
-        lib = hip.load()
-        g = g.to(_f32).contiguous()
-        d = torch.empty_like(low)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_iw_maxsquare_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, st.data_ptr(), g.data_ptr(),
-                                              d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_iw_maxsquare_up_bwd")
-        return d, None, None, None
-
-
-class _MultiCEUp(Function):
-    @staticmethod
-    def forward(ctx, low1, low2, ho, wo, thr):
-        low1 = _check_act(low1, "multi_ce_up")
-        low2 = _check_act(low2.detach(), "multi_ce_up")
-        c, hi, wi, ho, wo = _geom(low1, (ho, wo))
-        lib = hip.load()
-        out = torch.empty((), dtype=_f32, device=low1.device)
-        st = _stats(low1.device)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low1.device)
-        hip.check(lib.msl_multi_ce_up_fwd(low1.data_ptr(), low2.data_ptr(), c, hi, wi, ho, wo, float(thr),
-                                          out.data_ptr(), st.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_multi_ce_up_fwd")
-        ctx.save_for_backward(low1, low2, st)
-        ctx.geo = (c, hi, wi, ho, wo, float(thr))
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        low1, low2, st = ctx.saved_tensors
-        c, hi, wi, ho, wo, thr = ctx.geo
-        lib = hip.load()
-        g = g.to(_f32).contiguous()
-        d = torch.empty_like(low1)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low1.device)
-        hip.check(lib.msl_multi_ce_up_bwd(low1.data_ptr(), low2.data_ptr(), c, hi, wi, ho, wo, thr, st.data_ptr(),
-                                          g.data_ptr(), d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_multi_ce_up_bwd")
-        return d, None, None, None, None
-
-
-class _EntropyUp(Function):
-    @staticmethod
-    def forward(ctx, low, ho, wo):
-        low = _check_act(low, "entropy_up")
-        c, hi, wi, ho, wo = _geom(low, (ho, wo))
-        lib = hip.load()
-        out = torch.empty((), dtype=_f32, device=low.device)
-        st = _stats(low.device)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_entropy_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, out.data_ptr(), st.data_ptr(),
-                                         ws.data_ptr(), wsb, hip.stream_ptr()), "msl_entropy_up_fwd")
-        ctx.save_for_backward(low, st)
-        ctx.geo = (c, hi, wi, ho, wo)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        low, st = ctx.saved_tensors
-        c, hi, wi, ho, wo = ctx.geo
-        lib = hip.load()
-        g = g.to(_f32).contiguous()
-        d = torch.empty_like(low)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_entropy_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, st.data_ptr(), g.data_ptr(),
-                                         d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_entropy_up_bwd")
-        return d, None, None
-
-
-class _IWEntropyUp(Function):
-    @staticmethod
-    def forward(ctx, low, ho, wo, ratio):
-        low = _check_act(low, "iw_entropy_up")
-        c, hi, wi, ho, wo = _geom(low, (ho, wo))
-        lib = hip.load()
-        out = torch.empty((), dtype=_f32, device=low.device)
-        st = _stats(low.device)
-        hist = torch.empty(c, dtype=torch.int32, device=low.device)
-        weights = torch.empty(c, dtype=_f32, device=low.device)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_iw_entropy_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, float(ratio), out.data_ptr(),
-                                            st.data_ptr(), hist.data_ptr(), weights.data_ptr(), ws.data_ptr(),
-                                            wsb, hip.stream_ptr()), "msl_iw_entropy_up_fwd")
-        ctx.save_for_backward(low, st)
-        ctx.geo = (c, hi, wi, ho, wo)
-        ctx.mark_non_differentiable(hist, weights)
-        return out, hist, weights
-
-    @staticmethod
-    def backward(ctx, g, _gh, _gw):
-        low, st = ctx.saved_tensors
-        c, hi, wi, ho, wo = ctx.geo
-        lib = hip.load()
-        g = g.to(_f32).contiguous()
-        d = torch.empty_like(low)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_iw_entropy_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, st.data_ptr(), g.data_ptr(),
-                                            d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_iw_entropy_up_bwd")
-        return d, None, None, None
-
-
-class _HardCEUp(Function):
-    @staticmethod
-    def forward(ctx, low, ho, wo, thr):
-        low = _check_act(low, "hard_ce_up")
-        c, hi, wi, ho, wo = _geom(low, (ho, wo))
-        lib = hip.load()
-        out = torch.empty((), dtype=_f32, device=low.device)
-        st = _stats(low.device)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_hard_ce_up_fwd(low.data_ptr(), c, hi, wi, ho, wo, float(thr), out.data_ptr(),
-                                         st.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_hard_ce_up_fwd")
-        ctx.save_for_backward(low, st)
-        ctx.geo = (c, hi, wi, ho, wo, float(thr))
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        low, st = ctx.saved_tensors
-        c, hi, wi, ho, wo, thr = ctx.geo
-        lib = hip.load()
-        g = g.to(_f32).contiguous()
-        d = torch.empty_like(low)
-        wsb = lib.msl_loss_workspace(c, hi, wi, ho, wo)
-        ws = hip.workspace(wsb, low.device)
-        hip.check(lib.msl_hard_ce_up_bwd(low.data_ptr(), c, hi, wi, ho, wo, thr, st.data_ptr(), g.data_ptr(),
-                                         d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()),
-                  "msl_hard_ce_up_bwd")
-        return d, None, None, None
+        d = torch.empty_like(head[0])
+        wsb = lib.msl_loss_workspace(*geo[:5])
+        ws = hip.workspace(wsb, d.device)
+        name = f"msl_{kind}_up_bwd"
+        hip.check(getattr(lib, name)(*(t.data_ptr() for t in head), *geo, st.data_ptr(), g.data_ptr(),
+                                     d.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()), name)
+        return None, d, None, None, None, None
 
 
 def low_of(pred):
@@ -1235,38 +1056,38 @@ def loss_labels_up(low1, low2, out_hw, thr=0.95):
 
 
 def ce_up(low, labels, out_hw):
-    return _CEUp.apply(low, labels, int(out_hw[0]), int(out_hw[1]))
+    return _LossUp.apply("ce", low, labels, int(out_hw[0]), int(out_hw[1]), None)
 
 
 def maxsquare_up(low, out_hw):
-    return _MaxSquareUp.apply(low, int(out_hw[0]), int(out_hw[1]))
+    return _LossUp.apply("maxsquare", low, None, int(out_hw[0]), int(out_hw[1]), None)
 
 
 def iw_maxsquare_up(low, out_hw, ratio):
     """Returns (loss, hist int32[C], weights fp32[C])."""
-    return _IWMaxSquareUp.apply(low, int(out_hw[0]), int(out_hw[1]), float(ratio))
+    return _LossUp.apply("iw_maxsquare", low, None, int(out_hw[0]), int(out_hw[1]), float(ratio))
 
 
 def multi_ce_up(low1, low2, out_hw, thr):
-    return _MultiCEUp.apply(low1, low2, int(out_hw[0]), int(out_hw[1]), float(thr))
+    return _LossUp.apply("multi_ce", low1, low2, int(out_hw[0]), int(out_hw[1]), float(thr))
 
 
 def entropy_up(low, out_hw):
     """softCrossEntropy()(pred, softmax(pred)) of the upsampled logits (loss.py:17-35): the mean over
     C*H*W of -log_softmax * softmax, the gradient through both factors."""
-    return _EntropyUp.apply(low, int(out_hw[0]), int(out_hw[1]))
+    return _LossUp.apply("entropy", low, None, int(out_hw[0]), int(out_hw[1]), None)
 
 
 def iw_entropy_up(low, out_hw, ratio):
     """IWsoftCrossEntropy(ratio)(pred, softmax(pred)) (loss.py:37-67).  Returns (loss, hist int32[C] of
     the logits' argmax, weights fp32[C])."""
-    return _IWEntropyUp.apply(low, int(out_hw[0]), int(out_hw[1]), float(ratio))
+    return _LossUp.apply("iw_entropy", low, None, int(out_hw[0]), int(out_hw[1]), float(ratio))
 
 
 def hard_ce_up(low, out_hw, thr):
     """CE(pred, label) with the pseudo-label argmax p where max p > thr, else ignored
     (solve_gta5.py:185-199); nan with a zero gradient when no pixel passes."""
-    return _HardCEUp.apply(low, int(out_hw[0]), int(out_hw[1]), float(thr))
+    return _LossUp.apply("hard_ce", low, None, int(out_hw[0]), int(out_hw[1]), float(thr))
 
 
 def _pseudo(low, out_hw, thr, want_label, want_arg):
@@ -1457,8 +1278,7 @@ class _SoftCE(Function):
             hip.check(lib.msl_soft_ce_fwd(inputs.data_ptr(), target.data_ptr(), c, hw, float(ignore), out.data_ptr(),
                                           st.data_ptr(), ws.data_ptr(), wsb, hip.stream_ptr()), "msl_soft_ce_fwd")
             return out
-        hist = torch.empty(c, dtype=torch.int32, device=inputs.device)
-        weights = torch.empty(c, dtype=_f32, device=inputs.device)
+        hist, weights = _iw_outputs(c, inputs.device)
         hip.check(lib.msl_iw_soft_ce_fwd(inputs.data_ptr(), target.data_ptr(), c, hw, float(ignore), float(ratio),
                                          out.data_ptr(), st.data_ptr(), hist.data_ptr(), weights.data_ptr(),
                                          ws.data_ptr(), wsb, hip.stream_ptr()), "msl_iw_soft_ce_fwd")
@@ -1527,8 +1347,7 @@ class _IWMaxSquareProb(Function):
                 raise hip.MSLError("iw_maxsquare_prob: label must be int64 (N,H,W) with N=1")
         lib = hip.load()
         out = torch.empty((), dtype=_f32, device=prob.device)
-        hist = torch.empty(c, dtype=torch.int32, device=prob.device)
-        weights = torch.empty(c, dtype=_f32, device=prob.device)
+        hist, weights = _iw_outputs(c, prob.device)
         wsb = lib.msl_loss_workspace(c, 1, 1, 1, hw)
         ws = hip.workspace(wsb, prob.device)
         hip.check(lib.msl_iw_maxsquare_prob_fwd(prob.data_ptr(), hip.ptr(label), c, hw, float(ratio),

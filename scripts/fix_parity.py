@@ -7,7 +7,10 @@ bitwise comparison of two library builds (MSL_LIB_PATH) or settings that must ag
 
 Covered: the 3x3 and pointwise convs (y, dx, dW; dW also accumulated into a flat gradient buffer, one
 pointwise case per weight-gradient orientation and one 3x3 case), the ASPP head (ops.aspp2, 2048 -> 19,
-d 6 / 12), the stem, and the 2048 -> 512 data gradient with the masked residual in its epilogue."""
+d 6 / 12), the stem (also with an accumulating weight), a residual BN + ReLU whose affine parameters
+accumulate into a flat buffer, the 2048 -> 512 data gradient with the masked residual in its epilogue,
+and every loss of ops (loss, IW outputs and the logits' gradient): the host wrappers of ops.py issue
+these calls, so two versions of the package over one library must agree bit for bit too."""
 import argparse
 import os
 import sys
@@ -84,10 +87,48 @@ for nimg in (1, 2):
     x = torch.randn(1, 3, nimg, 257, 513, device=dev).mul_(60).requires_grad_()
     wt = weight(64, 3, 7, 7)
     record(f"stem 3->64 n{nimg}", ops.stem_conv(x, wt, 2, 3, ops.PackCache(pointwise=True)), x, [wt])
+    x = torch.randn(1, 3, nimg, 257, 513, device=dev).mul_(60).requires_grad_()
+    wt = weight(64, 3, 7, 7, acc=True)
+    record(f"stem 3->64 n{nimg} acc", ops.stem_conv(x, wt, 2, 3, ops.PackCache(pointwise=True)), x, [wt])
+    # a residual BN + ReLU whose affine parameters accumulate in place into a flat gradient buffer
+    bn = torch.nn.BatchNorm2d(256).to(dev).train()
+    bn.flat = FlatGrads([bn.weight, bn.bias], dev)
+    bn.flat.flat.normal_()
+    x, res = act(256, nimg, 65, 129), act(256, nimg, 65, 129)
+    record(f"bn_act 256 res relu n{nimg} acc", ops.bn_act(bn, x, residual=res, relu=True), x,
+           [res, bn.weight, bn.bias])
     # a layer4 identity block: conv1's 2048 -> 512 data gradient applies bn3's ReLU mask to the residual
     # gradient in its epilogue (ops.MaskedResidual; the bf16 math materialises it)
     blk = dm.Bottleneck(2048, 512, dilation=4).to(dev).train()
     x = act(2048, nimg, 65, 129) if nimg > 1 else torch.randn(1, 2048, 65, 129, device=dev).requires_grad_()
     record(f"block 2048/512 d4 n{nimg}", blk(x), x, list(blk.parameters()))
+
+# the losses: C = 19, the fused ones from 9 x 17 logits upsampled to 33 x 65, the others at 33 x 65
+C, LOW, UP = 19, (9, 17), (33, 65)
+labels = torch.randint(-1, C, (UP[0] * UP[1],), device=dev)
+low2 = torch.randn(1, C, *LOW, device=dev) * 4
+target = torch.softmax(torch.randn(1, C, *UP, device=dev) * 3, 1)
+LOSSES = {
+    "ce_up": (LOW, lambda t: ops.ce_up(t, labels, UP)),
+    "maxsquare_up": (LOW, lambda t: ops.maxsquare_up(t, UP)),
+    "iw_maxsquare_up": (LOW, lambda t: ops.iw_maxsquare_up(t, UP, 0.2)),
+    "multi_ce_up": (LOW, lambda t: ops.multi_ce_up(t, low2, UP, 0.5)),
+    "entropy_up": (LOW, lambda t: ops.entropy_up(t, UP)),
+    "iw_entropy_up": (LOW, lambda t: ops.iw_entropy_up(t, UP, 0.2)),
+    "hard_ce_up": (LOW, lambda t: ops.hard_ce_up(t, UP, 0.5)),
+    "soft_ce": (UP, lambda t: ops.soft_ce(t, target)),
+    "iw_soft_ce": (UP, lambda t: ops.iw_soft_ce(t, target, 0.2)),
+    "maxsquare_prob": (UP, lambda t: ops.maxsquare_prob(torch.softmax(t, 1))),
+    "iw_maxsquare_prob": (UP, lambda t: ops.iw_maxsquare_prob(torch.softmax(t, 1), labels, 0.2)),
+}
+for name, (hw, fn) in LOSSES.items():
+    low = (torch.randn(1, C, *hw, device=dev) * 4).requires_grad_()
+    res = fn(low)
+    loss, iw = (res[0], res[1:]) if isinstance(res, tuple) else (res, ())
+    (loss * 0.75).backward()
+    out[name + " loss"] = loss.detach().cpu()
+    out[name + " d low"] = low.grad.cpu()
+    for tag, t in zip(("hist", "weights"), iw):
+        out[f"{name} {tag}"] = t.cpu()
 torch.save(out, args.out)
 print(len(out), "tensors saved")

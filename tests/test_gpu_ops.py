@@ -898,6 +898,64 @@ def test_pconv_wgrad_accumulate_both_orientations(cin, cout, h, w, form):
         ops.set_f32_form(prev)
 
 
+@pytest.mark.parametrize("nimg", [1, 2])
+@pytest.mark.parametrize("kind,cin,cout,h,w,d", [
+    ("pconv", 48, 160, 9, 13, 0), ("pconv", 200, 328, 9, 31, 0), ("pconv", 328, 200, 9, 31, 0),
+    ("stem", 3, 64, 33, 47, 0), ("dconv", 32, 48, 9, 13, 2)])
+def test_conv_weight_gradient_sinks(kind, cin, cout, h, w, d, nimg, f32_form):
+    """The in-place weight-gradient path of ops.pconv, ops.stem_conv and one-branch ops.dconv3x3
+    (ops._wgrad_call): with the weight's .grad its slice of a FlatGrads buffer holding g0, the backward
+    leaves g0 + dW there (fp64 reference, the bound of the ops' own tests), hands autograd None for the
+    parameter, reports the parameter to the buffer once, and computes the bits of dx it computes for a
+    plain leaf weight.  The pointwise shapes cover both weight-gradient orientations and a ragged tile.
+    FlatGrads.notify runs a second time per backward from the buffer's own post-accumulate hook, which
+    autograd fires for a None gradient too: the op's reports are the calls beyond the hook's."""
+    from maxsquareloss_amd.utils.optim import FlatGrads
+    g = torch.Generator().manual_seed(cin * 11 + cout + nimg)
+    k = {"pconv": 1, "stem": 7, "dconv": 3}[kind]
+    conv = {"pconv": {}, "stem": dict(stride=2, padding=3), "dconv": dict(padding=d, dilation=d)}[kind]
+    x = torch.randn(1, cin, nimg, h, w, generator=g) * (50 if kind == "stem" else 1)
+    wt = torch.randn(cout, cin, k, k, generator=g) * 0.05
+    g0 = torch.randn(cout, cin, k, k, generator=g)
+    wr = wt.double().requires_grad_()
+    yr = torch.stack([F.conv2d(x[:, :, i].double(), wr, **conv) for i in range(nimg)], 2)  # per image
+    gy = torch.randn(yr.shape, generator=g)
+    yr.backward(gy.double())
+
+    def run(sink):
+        xg, gyg = (t.to(DEV) if nimg > 1 else t[:, :, 0].to(DEV) for t in (x, gy))
+        xg.requires_grad_()
+        wg = torch.nn.Parameter(wt.to(DEV))
+        received, notified, hooked = [], [], []
+        fg = None
+        if sink:
+            fg = FlatGrads([wg], DEV)
+            fg.flat.copy_(g0.reshape(-1))
+            inner = fg.notify
+            fg.notify = lambda i: (notified.append(i), inner(i))[1]
+            wg.register_post_accumulate_grad_hook(lambda p: hooked.append(p))
+        wg.register_hook(received.append)
+        if kind == "pconv":
+            y = ops.pconv(xg, wg, ops.PackCache(pointwise=True))
+        elif kind == "stem":
+            y = ops.stem_conv(xg, wg, 2, 3, ops.PackCache(pointwise=True))
+        else:
+            y = ops.dconv3x3(xg, wg, d, ops.PackCache())
+        y.backward(gyg)
+        torch.cuda.synchronize()
+        return xg.grad, wg, fg, received, notified, hooked
+
+    dx, wg, _, received, _, _ = run(False)
+    assert len(received) == 1 and received[0] is not None
+    assert _rel(wg.grad, wr.grad) < 1e-5
+    dx_s, wg_s, fg, received, notified, hooked = run(True)
+    assert wg_s.grad.data_ptr() == fg.flat.data_ptr()
+    assert _rel(fg.flat.view_as(wt), g0.double() + wr.grad) < 1e-5
+    assert received == [None]
+    assert notified.count(0) - len(hooked) == 1 and set(notified) == {0}
+    assert torch.equal(dx_s, dx)
+
+
 def _elem_err(out, ref, bound):
     """max over elements of |out - ref| / (the same conv of |operands|): the error relative to the
     element's own sum of |terms|, the measure fp32 accumulation is judged by."""
