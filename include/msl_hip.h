@@ -581,7 +581,8 @@ int msl_bn_bwd_am(const float* dy, const float* x, const float* y, const float* 
                   int accumulate_params, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream, float* absmax_dx);
 /* msl_bn_bwd_am that may take y = NULL with relu for a BN WITHOUT a residual: the fused kernel
  * then recomputes the ReLU mask from x (y > 0 <=> fma(x, invstd*gamma, fma(-mean, invstd*gamma,
- * beta)) > 0, the forward's own float operations on the saved mean / invstd, so the mask is
+ * beta)) > 0, the forward's own float operations on the saved mean / invstd - with invstd*gamma
+ * taken as 0 on a row whose every element equals its mean, as the forward takes it - so the mask is
  * identical) instead of reading y - one read of the map less.  beta = the forward's beta
  * (nullable = 0).  y = NULL needs msl_bn_uses_fused(c, p, training) and p <= 16384 (else
  * MSL_ERR_ARG); with y given it is msl_bn_bwd_am. */
@@ -610,6 +611,33 @@ int msl_bn_bwd_mask(const float* dy, const float* x, const uint64_t* relu_mask, 
                     float* dgamma, float* dbeta, int c, int p, int nimg, int training, int relu,
                     int accumulate_params, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream,
                     float* absmax_dx);
+
+/* The plan of a BN call, as a host-only query: no launch, no pointers to data, usable without a GPU.  It
+ * reports what msl_bn_fwd_mask (backward = 0) or the backward entry points (backward = 1) do with these
+ * arguments through the very functions the calls use (the refusals, the fused instantiation, the flat kernels'
+ * chunk), so it cannot drift from them.  The tests hold every kernel form and option to fp64 through it
+ * (tests/bn_form_cases.py).  Additive: ABI 3.  Replaces nothing in the reference. */
+typedef struct msl_bn_plan_info {
+  int status;   /* what the call returns: MSL_OK, MSL_ERR_ARG or MSL_ERR_WORKSPACE; the rest is 0 unless MSL_OK */
+  int fused;    /* 1 the one-block-per-channel kernels (one launch), 0 the flat ones (reduce + apply) */
+  int ept;      /* fused: elements per lane of the instantiation, 4, 9, 16 or 33; else 0 */
+  int joint;    /* fused: the joint two-image instantiation (nimg = 2), else the image loop */
+  int vec;      /* flat: the float4 body (every tensor operand 16-byte aligned), else scalar accesses */
+  int S;        /* fp64 partial sums per row (the workspace holds c * nimg * S * 2 doubles) */
+  int chunk;    /* elements per block of the flat apply kernels */
+  int max_rows; /* flat: the most rows one apply block stages in LDS (<= 256) */
+  int launches; /* kernel launches, in order: grid_x x grid_y blocks of `block` threads each */
+  int grid_x[2], grid_y[2], block[2];
+} msl_bn_plan_info;
+/* aligned: every tensor operand the call gives is 16-byte aligned.  Forward: has_mask / has_absmax = relu_mask /
+ * absmax given; entry, relu_src and has_dx are 0; the operands and running statistics count as given.
+ * Backward: entry 0 msl_bn_bwd / msl_bn_bwd_am, 1 msl_bn_bwd_am_beta, 2 msl_bn_bwd_mask; relu_src = where the
+ * ReLU mask comes from: 0 none (relu = 0), 1 y, 2 the mask bits (entry 2 alone), 3 recomputed (y = NULL);
+ * has_dx / has_absmax = dx / absmax_dx given; has_mask is 0.  ws_bytes as the call's.  Returns MSL_ERR_ARG
+ * (out untouched) for arguments that describe no call, else MSL_OK with the call's own status in out. */
+int msl_bn_plan(int backward, int c, int p, int nimg, int training, int relu, int aligned, int entry, int relu_src,
+                int has_dx, int has_absmax, int has_mask, size_t ws_bytes, const msl_forms* forms,
+                msl_bn_plan_info* out);
 
 /* ------------------------------------------------------------------------
  * Training-time evaluation (tools/train_source.py:280-283 + utils/eval.py:109-118): for one

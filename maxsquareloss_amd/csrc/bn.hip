@@ -111,7 +111,9 @@ struct BnArgs {
 };
 
 // Batch statistics of row r (channel r / NI of image r % NI) from the fp64 partial sums.
-__device__ __forceinline__ void bn_row_stats(const BnArgs& a, int r, float& mean, float& invstd, double& var) {
+// constant (optional): every element of the row equals its first (the squares sum to exactly 0)
+__device__ __forceinline__ void bn_row_stats(const BnArgs& a, int r, float& mean, float& invstd, double& var,
+                                             bool* constant = nullptr) {
   double s1 = 0.0, s2 = 0.0;
   for (int s = 0; s < a.S; ++s) {
     s1 += a.part[((long long)r * a.S + s) * 2];
@@ -124,6 +126,7 @@ __device__ __forceinline__ void bn_row_stats(const BnArgs& a, int r, float& mean
   if (var < 0.0) var = 0.0;
   mean = (float)(shift + dm);
   invstd = (float)(1.0 / sqrt(var + (double)a.eps));
+  if (constant) *constant = s2 == 0.0;
 }
 
 // (1 - m) * old + m * v with every operation rounded on its own: whether the compiler contracts
@@ -186,9 +189,10 @@ __global__ void __launch_bounds__(256) k_bn_apply(BnArgs a) {
     const int c = r / a.NI;
     const bool owner = (long long)r * a.P >= start;  // this block holds the row's first element
     float mean, invstd;
+    bool constant = false;
     if (a.training) {
       double var;
-      bn_row_stats(a, r, mean, invstd, var);
+      bn_row_stats(a, r, mean, invstd, var, &constant);
       if (owner && a.update_running && r % a.NI == 0) {
         for (int n = 0; n < a.NI; ++n) {
           float mn, is;
@@ -207,7 +211,8 @@ __global__ void __launch_bounds__(256) k_bn_apply(BnArgs a) {
       a.save_invstd[r] = invstd;
     }
     // y = x * alpha + beta'  (batch_norm_cpu_transform_input form)
-    const float alpha = invstd * (a.gamma ? a.gamma[c] : 1.f);
+    // a constant row normalises to exactly 0, y = beta: alpha = 0 (see bn_fwd_rows)
+    const float alpha = constant ? 0.f : invstd * (a.gamma ? a.gamma[c] : 1.f);
     coef[0][threadIdx.x] = alpha;
     coef[1][threadIdx.x] = (a.beta ? a.beta[c] : 0.f) - mean * alpha;
   }
@@ -600,7 +605,11 @@ __device__ __forceinline__ void bn_fwd_rows(const BnArgs& a, int c, int img0, do
       a.save_mean[r] = mean;
       a.save_invstd[r] = invstd;
     }
-    alpha[b] = invstd * (a.gamma ? a.gamma[c] : 1.f);
+    // A row whose elements all equal its first (the squares sum to exactly 0; every row of one pixel) normalises to
+    // exactly 0, so y = beta (+ residual): alpha = 0.  With invstd = 1 / sqrt(eps) = 316 the shifted form below would
+    // cancel x * alpha against the rounded mean * alpha and leave up to half an ulp of it in y (4.9e-4 at x = 40;
+    // tests/test_gpu_bn_forms.py at p = 1).  Every other row keeps its bits.
+    alpha[b] = s[2 * b + 1] == 0.0 ? 0.f : invstd * (a.gamma ? a.gamma[c] : 1.f);
     bsh[b] = __fmaf_rn(-mean, alpha[b], a.beta ? a.beta[c] : 0.f);
   }
 #pragma unroll
@@ -751,10 +760,21 @@ __device__ __forceinline__ void bn_bwd_rows(const BnBwdArgs& a, int c, int img0,
       }
     } else if (a.relu) {  // y > 0 recomputed with k_bn_fwd_fused's operations (its alpha, bsh)
       if constexpr (EPT <= kBnRemaskMaxEpt) {  // (the 33-element form spills twice as much with it)
-        const float bsh = __fmaf_rn(-mean[b], w, a.beta ? a.beta[c] : 0.f);
+        // A constant row - every element equals the saved mean - got alpha = 0 in the forward: y = beta.  Lanes past
+        // the row hold 0 and are not range-tested here: a row of zeros and copies of its (nonzero) fp32 mean would
+        // need fewer than 2^-25 of its elements zero, more than these forms hold (P <= 16384)
+        float wf = w;
+        if (a.x[(long long)r * P] == mean[b]) {  // (block-uniform: no row of the workload gets past its first element)
+          int differs = 0;
+#pragma unroll
+          for (int j = 0; j < EPT; ++j)
+            if (xv[b][j] != mean[b] && xv[b][j] != 0.f) differs = 1;
+          if (!__syncthreads_or(differs)) wf = 0.f;
+        }
+        const float bsh = __fmaf_rn(-mean[b], wf, a.beta ? a.beta[c] : 0.f);
 #pragma unroll
         for (int j = 0; j < EPT; ++j)
-          if (!(__fmaf_rn(xv[b][j], w, bsh) > 0.f)) g[b][j] = 0.f;
+          if (!(__fmaf_rn(xv[b][j], wf, bsh) > 0.f)) g[b][j] = 0.f;
       }
     }
     double sg = 0.0, sgx = 0.0;
@@ -840,23 +860,128 @@ constexpr int kBnJointPair = 1;
 constexpr bool kBnJoint16Fwd = true;
 constexpr bool kBnJoint16Bwd = false;
 constexpr int kBnJointMaxC = 256;
+// The fused instantiation of a (c, p, nimg) call: elements per lane and whether the pair runs the joint two-image
+// kernel (joint16: whether the direction builds it at 16 elements).  The launch and msl_bn_plan both ask this.
+struct BnFusedSel {
+  int ept;
+  bool joint;
+};
+static BnFusedSel bn_fused_select(int c, int p, int nimg, bool joint16) {
+  const bool joint = kBnJointPair && nimg == 2 && c <= kBnJointMaxC;
+  if (p > 16 * kBnFusedThreads) return {33, false};
+  if (p <= 4 * kBnFusedThreads) return {4, joint};
+  if (p <= 9 * kBnFusedThreads) return {9, joint};
+  return {16, joint && joint16};
+}
 // (one MSL_LAUNCH per kernel: each is checked against its own launch bound)
 template <auto K4, auto K9, auto K16, auto K33, auto J4, auto J9, auto J16, typename A>
-static int bn_launch_fused(int c, int p, hipStream_t st, const A& a) {
-  const bool joint = kBnJointPair && a.NI == 2 && c <= kBnJointMaxC;
+static int bn_launch_fused(int c, BnFusedSel sel, hipStream_t st, const A& a) {
   const dim3 grid(c), block(kBnFusedThreads);
-  if (p > 16 * kBnFusedThreads) MSL_LAUNCH(K33, grid, block, 0, st, a);
-  else if (p <= 4 * kBnFusedThreads && joint) MSL_LAUNCH(J4, grid, block, 0, st, a);
-  else if (p <= 4 * kBnFusedThreads) MSL_LAUNCH(K4, grid, block, 0, st, a);
-  else if (p <= 9 * kBnFusedThreads && joint) MSL_LAUNCH(J9, grid, block, 0, st, a);
-  else if (p <= 9 * kBnFusedThreads) MSL_LAUNCH(K9, grid, block, 0, st, a);
-  else if (joint) MSL_LAUNCH(J16, grid, block, 0, st, a);
+  if (sel.ept == 33) MSL_LAUNCH(K33, grid, block, 0, st, a);
+  else if (sel.ept == 4 && sel.joint) MSL_LAUNCH(J4, grid, block, 0, st, a);
+  else if (sel.ept == 4) MSL_LAUNCH(K4, grid, block, 0, st, a);
+  else if (sel.ept == 9 && sel.joint) MSL_LAUNCH(J9, grid, block, 0, st, a);
+  else if (sel.ept == 9) MSL_LAUNCH(K9, grid, block, 0, st, a);
+  else if (sel.joint) MSL_LAUNCH(J16, grid, block, 0, st, a);
   else MSL_LAUNCH(K16, grid, block, 0, st, a);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// What a BN call does, from the arguments that decide it alone (no pointer is read): the entry points launch from
+// this record and msl_bn_plan reports it, so the two cannot drift.
+struct BnPlan {
+  int status;      // the refusal, or MSL_OK
+  bool fused;      // the one-block-per-channel kernels
+  BnFusedSel sel;  // their instantiation (fused)
+  bool vec;        // the flat kernels' float4 body (every tensor operand 16-byte aligned)
+  int S, chunk, R; // statistics parts per row, elements per flat block, rows
+  unsigned blocks; // flat apply blocks
+};
+
+// msl_bn_fwd_mask's refusals and plan.  has_*: the pointer is given; operands: x, y, save_mean, save_invstd.
+static BnPlan bn_fwd_plan(bool operands, bool has_running, bool has_mask, bool aligned, int c, int p, int nimg,
+                          int training, int update_running, int relu, const msl_forms* forms, size_t ws_bytes) {
+  BnPlan pl = {};
+  pl.status = MSL_ERR_ARG;
+  if (!operands || c < 1 || p < 1 || nimg < 1 || (long long)c * nimg >= (1LL << 31)) return pl;
+  if ((!training || update_running) && !has_running) return pl;
+  if (training && ws_bytes < msl_bn_workspace(c, p, nimg)) {
+    pl.status = MSL_ERR_WORKSPACE;
+    return pl;
+  }
+  if (forms_bad(forms)) return pl;
+  pl.fused = training && bn_fused_enabled(forms) && bn_fused_shape(c, p);
+  if (has_mask && !(pl.fused && relu)) return pl;  // the bits come from the fused kernels
+  pl.status = MSL_OK;
+  pl.S = bn_splits(p);
+  pl.R = c * nimg;
+  pl.chunk = bn_flat_chunk(p);
+  pl.vec = aligned;
+  if (pl.fused) pl.sel = bn_fused_select(c, p, nimg, kBnJoint16Fwd);
+  else pl.blocks = (unsigned)cdiv((long long)pl.R * p, (long long)pl.chunk);
+  return pl;
+}
+
+// The ReLU source of a backward call: none, the forward's y, its mask bits, or recomputed from x (y = NULL)
+enum { kBnReluNone = 0, kBnReluY = 1, kBnReluBits = 2, kBnReluRecompute = 3 };
+// The backward entry points: msl_bn_bwd / msl_bn_bwd_am (y required with relu), msl_bn_bwd_am_beta, msl_bn_bwd_mask
+enum { kBnEntryAm = 0, kBnEntryBeta = 1, kBnEntryMask = 2 };
+// what the entry point itself refuses ahead of bn_bwd
+static int bn_bwd_entry_status(int entry, int relu, bool has_y, bool has_mask) {
+  if (entry == kBnEntryAm && relu && !has_y) return MSL_ERR_ARG;
+  if (entry == kBnEntryMask && (!has_mask || !relu)) return MSL_ERR_ARG;
+  return MSL_OK;
+}
+
+// bn_bwd's refusals and plan.  operands: dy, x, save_mean, save_invstd.
+static BnPlan bn_bwd_plan(bool operands, bool has_y, bool has_mask, bool has_dx, bool has_absmax, bool aligned, int c,
+                          int p, int nimg, int training, int relu, const msl_forms* forms, size_t ws_bytes) {
+  BnPlan pl = {};
+  pl.status = MSL_ERR_ARG;
+  if (!operands || c < 1 || p < 1 || nimg < 1 || (long long)c * nimg >= (1LL << 31)) return pl;
+  if (forms_bad(forms)) return pl;
+  pl.fused = training && bn_fused_enabled(forms) && bn_fused_shape(c, p);
+  if (has_mask && !(pl.fused && relu)) return pl;  // the bits are read by the fused kernels
+  // the mask recompute is the fused kernels' alone, up to 16 elements per lane
+  if (relu && !has_y && !has_mask && !(pl.fused && p <= kBnRemaskMaxEpt * kBnFusedThreads)) return pl;
+  if (has_absmax && !has_dx) return pl;
+  if (ws_bytes < msl_bn_workspace(c, p, nimg)) {
+    pl.status = MSL_ERR_WORKSPACE;
+    return pl;
+  }
+  pl.status = MSL_OK;
+  pl.S = bn_splits(p);
+  pl.R = c * nimg;
+  pl.chunk = bn_flat_chunk(p);
+  pl.vec = aligned;
+  if (pl.fused) pl.sel = bn_fused_select(c, p, nimg, kBnJoint16Bwd);
+  else pl.blocks = (unsigned)cdiv((long long)pl.R * p, (long long)pl.chunk);
+  return pl;
+}
+
+// The most rows one block of the flat apply kernels stages (their nch): block b covers elements [b * chunk,
+// (b + 1) * chunk) of R rows of p.  The blocks' offsets within a row repeat after p / gcd(chunk, p) blocks.
+static int bn_flat_max_rows(int R, int p, int chunk) {
+  const long long N = (long long)R * p;
+  const long long blocks = (N + chunk - 1) / chunk;
+  long long g = chunk, h = p;
+  while (h) {
+    const long long t = g % h;
+    g = h;
+    h = t;
+  }
+  const long long period = std::min(blocks, (long long)p / g);
+  int most = 0;
+  auto rows = [&](long long b) {
+    const long long start = b * chunk, end = std::min(N, start + chunk);
+    return (int)((end - 1) / p - start / p) + 1;
+  };
+  for (long long b = 0; b < period; ++b) most = std::max(most, rows(b));
+  return std::max(most, rows(blocks - 1));
+}
 
 }  // namespace msl
 
@@ -903,18 +1028,15 @@ int msl_bn_fwd_mask(const float* x, const float* gamma, const float* beta, const
                     float* save_mean, float* save_invstd, int c, int p, int nimg, int training,
                     int update_running, float momentum, float eps, int relu, const msl_forms* forms, void* ws,
                     size_t ws_bytes, msl_stream_t stream, float* absmax, uint64_t* relu_mask) {
-  if (!x || !y || !save_mean || !save_invstd || c < 1 || p < 1 || nimg < 1 || (long long)c * nimg >= (1LL << 31))
-    return MSL_ERR_ARG;
-  if ((!training || update_running) && (!running_mean || !running_var)) return MSL_ERR_ARG;
+  const BnPlan pl = bn_fwd_plan(x && y && save_mean && save_invstd, running_mean && running_var, relu_mask != nullptr,
+                                al16(x) && al16(y) && (!residual || al16(residual)), c, p, nimg, training,
+                                update_running, relu, forms, ws_bytes);
+  if (pl.status != MSL_OK) return pl.status;
   hipStream_t st = as_stream(stream);
-  const int S = bn_splits(p);
-  const int R = c * nimg;  // rows (channel, image)
-  if (training && ws_bytes < msl_bn_workspace(c, p, nimg)) return MSL_ERR_WORKSPACE;
+  const int S = pl.S;
+  const int R = pl.R;  // rows (channel, image)
   double* part = (double*)ws;
-  const bool vec = al16(x) && al16(y) && (!residual || al16(residual));
-  if (forms_bad(forms)) return MSL_ERR_ARG;
-  const bool fused = training && bn_fused_enabled(forms) && bn_fused_shape(c, p);
-  if (relu_mask && !(fused && relu)) return MSL_ERR_ARG;  // the bits come from the fused kernels
+  const bool vec = pl.vec, fused = pl.fused;
   if (training && !fused) {
     if (vec)
       MSL_LAUNCH(k_bn_stats<true>, dim3(R, S), dim3(256), 0, st, x, p, S, part, absmax, nimg);
@@ -941,7 +1063,7 @@ int msl_bn_fwd_mask(const float* x, const float* gamma, const float* beta, const
   a.NI = nimg;
   a.P = p;
   a.S = S;
-  a.chunk = bn_flat_chunk(p);
+  a.chunk = pl.chunk;
   a.relu = relu;
   a.training = training;
   a.update_running = update_running;
@@ -951,8 +1073,8 @@ int msl_bn_fwd_mask(const float* x, const float* gamma, const float* beta, const
   a.mask = reinterpret_cast<unsigned long long*>(relu_mask);
   if (fused)
     return bn_launch_fused<k_bn_fwd_fused<4>, k_bn_fwd_fused<9>, k_bn_fwd_fused<16>, k_bn_fwd_fused<33>,
-                           k_bn_fwd_fused<4, true>, k_bn_fwd_fused<9, true>, k_bn_fwd_fused<16, kBnJoint16Fwd>>(c, p, st, a);
-  const unsigned blocks = (unsigned)cdiv((long long)R * p, (long long)a.chunk);
+                           k_bn_fwd_fused<4, true>, k_bn_fwd_fused<9, true>, k_bn_fwd_fused<16, kBnJoint16Fwd>>(c, pl.sel, st, a);
+  const unsigned blocks = pl.blocks;
   if (vec)
     MSL_LAUNCH(k_bn_apply<true>, dim3(blocks), dim3(256), 0, st, a);
   else
@@ -973,7 +1095,7 @@ int msl_bn_bwd_am(const float* dy, const float* x, const float* y, const float* 
                   const float* save_mean, const float* save_invstd, float* dx, float* dres,
                   float* dgamma, float* dbeta, int c, int p, int nimg, int training, int relu,
                   int accumulate_params, const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream, float* absmax_dx) {
-  if (relu && !y) return MSL_ERR_ARG;
+  if (bn_bwd_entry_status(kBnEntryAm, relu, y != nullptr, false) != MSL_OK) return MSL_ERR_ARG;
   return msl_bn_bwd_am_beta(dy, x, y, gamma, nullptr, save_mean, save_invstd, dx, dres, dgamma, dbeta, c, p, nimg,
                             training, relu, accumulate_params, forms, ws, ws_bytes, stream, absmax_dx);
 }
@@ -982,18 +1104,16 @@ static int bn_bwd(const float* dy, const float* x, const float* y, const uint64_
                   const float* beta, const float* save_mean, const float* save_invstd, float* dx, float* dres,
                   float* dgamma, float* dbeta, int c, int p, int nimg, int training, int relu, int accumulate_params,
                   const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream, float* absmax_dx) {
-  if (!dy || !x || !save_mean || !save_invstd || c < 1 || p < 1 || nimg < 1 || (long long)c * nimg >= (1LL << 31))
-    return MSL_ERR_ARG;
-  if (forms_bad(forms)) return MSL_ERR_ARG;
-  const bool fused = training && bn_fused_enabled(forms) && bn_fused_shape(c, p);
-  if (relu_mask && !(fused && relu)) return MSL_ERR_ARG;  // the bits are read by the fused kernels
-  // the mask recompute is the fused kernels' alone, up to 16 elements per lane
-  if (relu && !y && !relu_mask && !(fused && p <= kBnRemaskMaxEpt * kBnFusedThreads)) return MSL_ERR_ARG;
-  if (absmax_dx && !dx) return MSL_ERR_ARG;
-  if (ws_bytes < msl_bn_workspace(c, p, nimg)) return MSL_ERR_WORKSPACE;
+  // (the alignment counts for the flat kernels alone; they read y only with relu)
+  const BnPlan pl = bn_bwd_plan(dy && x && save_mean && save_invstd, y != nullptr, relu_mask != nullptr, dx != nullptr,
+                                absmax_dx != nullptr,
+                                al16(dy) && al16(x) && (!relu || al16(y)) && (!dx || al16(dx)) && (!dres || al16(dres)),
+                                c, p, nimg, training, relu, forms, ws_bytes);
+  if (pl.status != MSL_OK) return pl.status;
+  const bool fused = pl.fused;
   hipStream_t st = as_stream(stream);
-  const int S = bn_splits(p);
-  const int R = c * nimg;  // rows (channel, image)
+  const int S = pl.S;
+  const int R = pl.R;  // rows (channel, image)
   BnBwdArgs a;
   a.dy = dy;
   a.x = x;
@@ -1011,7 +1131,7 @@ static int bn_bwd(const float* dy, const float* x, const float* y, const uint64_
   a.NI = nimg;
   a.P = p;
   a.S = S;
-  a.chunk = bn_flat_chunk(p);
+  a.chunk = pl.chunk;
   a.relu = relu;
   a.training = training;
   a.accumulate = accumulate_params;
@@ -1019,9 +1139,9 @@ static int bn_bwd(const float* dy, const float* x, const float* y, const uint64_
   a.mask = reinterpret_cast<const unsigned long long*>(relu_mask);
   if (fused)
     return bn_launch_fused<k_bn_bwd_fused<4>, k_bn_bwd_fused<9>, k_bn_bwd_fused<16>, k_bn_bwd_fused<33>,
-                           k_bn_bwd_fused<4, true>, k_bn_bwd_fused<9, true>, k_bn_bwd_fused<16, kBnJoint16Bwd>>(c, p, st, a);
-  const bool vec = al16(dy) && al16(x) && (!relu || al16(y)) && (!dx || al16(dx)) && (!dres || al16(dres));
-  const unsigned blocks = (unsigned)cdiv((long long)R * p, (long long)a.chunk);
+                           k_bn_bwd_fused<4, true>, k_bn_bwd_fused<9, true>, k_bn_bwd_fused<16, kBnJoint16Bwd>>(c, pl.sel, st, a);
+  const bool vec = pl.vec;
+  const unsigned blocks = pl.blocks;
   if (vec) {
     MSL_LAUNCH(k_bn_bwd_reduce<true>, dim3(R, S), dim3(256), 0, st, a);
     MSL_CHECK_LAUNCH();
@@ -1048,9 +1168,57 @@ int msl_bn_bwd_mask(const float* dy, const float* x, const uint64_t* relu_mask, 
                     const float* save_mean, const float* save_invstd, float* dx, float* dres, float* dgamma,
                     float* dbeta, int c, int p, int nimg, int training, int relu, int accumulate_params,
                     const msl_forms* forms, void* ws, size_t ws_bytes, msl_stream_t stream, float* absmax_dx) {
-  if (!relu_mask || !relu) return MSL_ERR_ARG;
+  if (bn_bwd_entry_status(kBnEntryMask, relu, false, relu_mask != nullptr) != MSL_OK) return MSL_ERR_ARG;
   return bn_bwd(dy, x, nullptr, relu_mask, gamma, beta, save_mean, save_invstd, dx, dres, dgamma, dbeta, c, p, nimg,
                 training, relu, accumulate_params, forms, ws, ws_bytes, stream, absmax_dx);
+}
+
+int msl_bn_plan(int backward, int c, int p, int nimg, int training, int relu, int aligned, int entry, int relu_src,
+                int has_dx, int has_absmax, int has_mask, size_t ws_bytes, const msl_forms* forms,
+                msl_bn_plan_info* out) {
+  auto flag = [](int v) { return v == 0 || v == 1; };
+  if (!out || !flag(backward) || !flag(training) || !flag(relu) || !flag(aligned) || !flag(has_dx) || !flag(has_absmax) ||
+      !flag(has_mask))
+    return MSL_ERR_ARG;
+  if (entry < kBnEntryAm || entry > kBnEntryMask || relu_src < kBnReluNone || relu_src > kBnReluRecompute)
+    return MSL_ERR_ARG;
+  BnPlan pl;
+  if (backward) {
+    // a call with relu names its source; the bits come through msl_bn_bwd_mask alone, which takes no y
+    if (has_mask || (relu && relu_src == kBnReluNone) || ((relu_src == kBnReluBits) != (entry == kBnEntryMask)))
+      return MSL_ERR_ARG;
+    const bool has_y = relu_src == kBnReluY, bits = relu_src == kBnReluBits;
+    pl = {};
+    pl.status = bn_bwd_entry_status(entry, relu, has_y, bits);
+    if (pl.status == MSL_OK)
+      pl = bn_bwd_plan(true, has_y, bits, has_dx, has_absmax, aligned, c, p, nimg, training, relu, forms, ws_bytes);
+  } else {
+    if (entry != 0 || relu_src != kBnReluNone || has_dx) return MSL_ERR_ARG;
+    pl = bn_fwd_plan(true, true, has_mask, aligned, c, p, nimg, training, 1, relu, forms, ws_bytes);
+  }
+  *out = msl_bn_plan_info{};
+  out->status = pl.status;
+  if (pl.status != MSL_OK) return MSL_OK;
+  out->fused = pl.fused;
+  out->S = pl.S;
+  out->chunk = pl.chunk;
+  auto launch = [&](unsigned gx, unsigned gy, int block) {
+    out->grid_x[out->launches] = (int)gx;
+    out->grid_y[out->launches] = (int)gy;
+    out->block[out->launches++] = block;
+  };
+  if (pl.fused) {
+    out->ept = pl.sel.ept;
+    out->joint = pl.sel.joint;
+    launch(c, 1, kBnFusedThreads);
+    return MSL_OK;
+  }
+  out->vec = pl.vec;
+  out->max_rows = bn_flat_max_rows(pl.R, p, pl.chunk);
+  if (backward || training) launch(pl.R, pl.S, 256);                // k_bn_bwd_reduce / k_bn_stats
+  else if (has_absmax) launch(cdiv(c, 256), 1, 256);                // k_zero_rows
+  launch(pl.blocks, 1, 256);                                        // k_bn_bwd_apply / k_bn_apply
+  return MSL_OK;
 }
 
 }  // extern "C"

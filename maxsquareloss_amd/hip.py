@@ -110,6 +110,7 @@ SIGNATURES = {
     "msl_bn_relu_mask_bytes": (c_sz, [c_int] * 3),
     "msl_bn_fwd_mask": (c_int, [c_p] * 10 + [c_int] * 5 + [c_f, c_f, c_int, c_p, c_p, c_sz, c_p, c_p, c_p]),
     "msl_bn_bwd_mask": (c_int, [c_p] * 11 + [c_int] * 6 + [c_p, c_p, c_sz, c_p, c_p]),
+    "msl_bn_plan": (c_int, [c_int] * 12 + [c_sz, c_p, c_p]),
     "msl_image_transform": (c_int, [c_p, c_int, c_int, c_int, c_f, c_f, c_f, c_p, c_p]),
     "msl_label_transform": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
     "msl_resize_workspace": (c_sz, [c_int, c_int]),
@@ -268,6 +269,31 @@ def conv_wgrad_plan(family, nbranch, taps, cin, cout, h, w, nimg, has_dbias=0, x
     fm = forms() if forms_ is None else ctypes.addressof(forms_)
     check(load(require_gpu=False).msl_conv_wgrad_plan(family, nbranch, taps, cin, cout, h, w, nimg, has_dbias, x_npart,
                                                       dy_npart, fm, ctypes.addressof(out)), "msl_conv_wgrad_plan")
+    return out
+
+
+class BnPlan(ctypes.Structure):
+    """msl_bn_plan_info: the plan of one BN call (msl_bn_plan; host only)."""
+    _fields_ = [(n, c_int) for n in ("status", "fused", "ept", "joint", "vec", "S", "chunk", "max_rows", "launches")] + [
+        ("grid_x", c_int * 2), ("grid_y", c_int * 2), ("block", c_int * 2)]
+
+
+BN_RELU_SOURCES = {"none": 0, "y": 1, "bits": 2, "recompute": 3}
+BN_BWD_ENTRIES = {"am": 0, "am_beta": 1, "mask": 2}
+
+
+def bn_plan(backward, c, p, nimg, training, relu, aligned=1, entry="am", relu_src="none", has_dx=0, has_absmax=0,
+            has_mask=0, ws_bytes=None, forms_=None):
+    """The plan of a BN call as a BnPlan (no GPU needed); `forms_` defaults to FORMS, `ws_bytes` to what
+    msl_bn_workspace asks.  The call's own refusal is in .status; arguments that describe no call raise."""
+    lib = load(require_gpu=False)
+    out = BnPlan()
+    fm = forms() if forms_ is None else ctypes.addressof(forms_)
+    if ws_bytes is None:
+        ws_bytes = lib.msl_bn_workspace(c, p, nimg)
+    check(lib.msl_bn_plan(int(backward), c, p, nimg, int(training), int(relu), int(aligned), BN_BWD_ENTRIES[entry],
+                          BN_RELU_SOURCES[relu_src], int(has_dx), int(has_absmax), int(has_mask), ws_bytes, fm,
+                          ctypes.addressof(out)), "msl_bn_plan")
     return out
 
 
