@@ -494,7 +494,7 @@ static FwdPlan plan_fwd(int math, int nbranch, int taps, int cimg, int M, int P,
         f.G = 2;
         f.stages = 3;
       }
-    } else if (!f.acc) {  // (no 3x3 call accumulates; the 128-row accumulating BD / BP forms are not instantiated)
+    } else if (!f.acc) {  // (no 3x3 call accumulates; no 128-row accumulating 3x3 form - LDS, BD or BP - is built)
       f.bform = bp_form(taps, M, math == kMathH1P) ? kBPre : bd ? kBDirect : kBLds;
     }
   }
@@ -533,8 +533,10 @@ static float* ws_partials(void* ws, size_t ws_bytes, int k) {  // k-th partials 
 
 // ---------------------------------------------------------------- forward form: the kernels
 // Every instantiation of the stream-K kernel, keyed by its own template arguments, with its launch bound
-// (MSL_LAUNCH_ENTRY).  k_igemm_fwd_sk2 is the same kernel held to two waves per SIMD (the f16 forms).  A
-// plan whose form has no row here is MSL_ERR_SHAPE.
+// (MSL_LAUNCH_ENTRY).  k_igemm_fwd_sk2 is the same kernel held to two waves per SIMD (the f16 forms).  Only rows
+// that a call through some entry point launches are built (tests/test_conv_forms.py); a plan whose form has no row
+// here is MSL_ERR_SHAPE: an accumulate epilogue in the bf16 math (its entry points take no accumulate flag) or on a
+// 128-row tile that is not pointwise (no 3x3 call accumulates).
 struct SkKernel {
   SkForm form;
   void (*fn)(FwdArgs, SkArgs);
@@ -547,21 +549,18 @@ struct SkKernel {
   {{BM, G, ST, 1, 4, PW, MT, ACC, BF},       \
    k_igemm_fwd_sk2<BM, kSkBN, G, ST, 1, 4, PW, MT, ACC, (BF) != kBLds, (BF) == kBPre>}
 #define MSL_SK2_BOTH(BM, G, ST, PW, MT, BF) MSL_SK2(BM, G, ST, PW, MT, false, BF), MSL_SK2(BM, G, ST, PW, MT, true, BF)
-// the f16x3 / fp16 rows they share: 64-row tiles in every operand form, 128-row 3x3 and pointwise tiles
+// the f16x3 / fp16 rows they share: 64-row tiles (LDS and BD), 128-row 3x3 tiles in every operand form, pointwise
 #define MSL_SK2_F16(MT)                                                                                      \
   MSL_SK2_BOTH(64, 1, 4, false, MT, kBLds), MSL_SK2_BOTH(64, 1, 4, false, MT, kBDirect),                      \
-  MSL_SK2_BOTH(64, 1, 4, false, MT, kBPre), /* (64-row BP: built since r03, chosen by no plan) */             \
-  MSL_SK2_BOTH(128, 1, 4, false, MT, kBLds), MSL_SK2(128, 1, 4, false, MT, false, kBDirect),                  \
+  MSL_SK2(128, 1, 4, false, MT, false, kBLds), MSL_SK2(128, 1, 4, false, MT, false, kBDirect),                \
   MSL_SK2(128, 1, 4, false, MT, false, kBPre), MSL_SK2_BOTH(128, 1, 4, true, MT, kBLds)
 static SkKernel kSkKernels[] = {
     MSL_SK_BOTH(128, 2, 2, 2, 2, kMathF32), MSL_SK_BOTH(128, 1, 3, 2, 2, kMathF32),
     MSL_SK_BOTH(64, 2, 2, 2, 2, kMathF32), MSL_SK_BOTH(64, 1, 3, 2, 2, kMathF32),
     MSL_SK_BOTH(32, 2, 2, 1, 4, kMathF32),
-    MSL_SK_BOTH(128, 2, 2, 2, 2, kMathBf16), MSL_SK_BOTH(128, 1, 3, 2, 2, kMathBf16),
-    MSL_SK_BOTH(64, 2, 2, 2, 2, kMathBf16), MSL_SK_BOTH(64, 1, 3, 2, 2, kMathBf16),
-    MSL_SK_BOTH(32, 2, 2, 1, 4, kMathBf16),
-    // (the in-loop bf16x6 split: built since r01, chosen by no plan since the x6 form reads pre-split weights)
-    MSL_SK_BOTH(128, 2, 2, 2, 2, kMathX6), MSL_SK_BOTH(128, 1, 3, 2, 2, kMathX6),
+    MSL_SK(128, 2, 2, 2, 2, kMathBf16, false), MSL_SK(128, 1, 3, 2, 2, kMathBf16, false),
+    MSL_SK(64, 2, 2, 2, 2, kMathBf16, false), MSL_SK(64, 1, 3, 2, 2, kMathBf16, false),
+    MSL_SK(32, 2, 2, 1, 4, kMathBf16, false),
     MSL_SK_BOTH(128, 1, 4, 2, 2, kMathX6P),
     MSL_SK2_F16(kMathH3P), MSL_SK2_BOTH(256, 1, 3, true, kMathH3P, kBLds),
     MSL_SK2_F16(kMathH1P), MSL_SK2_BOTH(128, 2, 3, true, kMathH1P, kBLds),

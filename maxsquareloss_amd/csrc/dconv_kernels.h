@@ -1,15 +1,12 @@
 // Implicit-GEMM kernel templates for the dilated 3x3 conv (design notes in dconv.hip).
 // Included by dconv.hip (libmsl_hip.so).
 #pragma once
-#include <type_traits>
-
 #include "msl_internal.h"
 
 namespace msl {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kSc1 = 16;  // buffer-op cache policy: sc1 (bypass L1, drop from L2 on store)
 
 constexpr int kCB = 16;        // image channels per forward K-group (one tap, 16 channels)
 constexpr int kPackPad = 128;  // packed-weight row padding (>= any BM)
@@ -50,15 +47,6 @@ __device__ __forceinline__ float acc_masked(const FwdArgs& a, int m, int n) {
   const unsigned long long w = a.accmask[(long long)(m * a.accni + img) * ((hw + 63) >> 6) + (px >> 6)];
   return ((w >> (px & 63)) & 1ull) ? a.accres[(long long)m * a.P + n] : 0.f;
 }
-
-struct WgradArgs {
-  const float* dy;  // [M][P]
-  const float* x;   // [N][P]
-  float* C;         // dW [nbranch][M][N][taps] or slabs of that
-  int M, N, H, W, P, dil0, dil1, ntap, ksteps, kps, accumulate;
-  int taps;         // taps per branch: 9, or 1 for a pointwise conv (dil0 = 0)
-  long long slab, cbranch;
-};
 
 // acc[i][j] += A_tile(kk..kk+BK) x B_tile over one LDS stage; A at As[k][m], B at Bs[k][n].
 // All of the stage's operand reads are issued before the first MFMA, so the LDS latency of
@@ -236,12 +224,6 @@ __device__ __forceinline__ void split2h_scaled(Split2h& out, const float (&v)[8]
   out.lo = lo.h;
 }
 
-// the plain image-operand map of the BD stage (x -> x * s): split through split2h_scaled
-struct ScaleXf {
-  float s;
-  __device__ __forceinline__ float operator()(int, float v) const { return v * s; }
-};
-
 __device__ __forceinline__ f32x16 mfma_h3(const Split2h& a, const Split2h& b, f32x16 c) {
   c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.lo, b.hi, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.hi, b.lo, c, 0, 0, 0);
@@ -331,30 +313,6 @@ __device__ __forceinline__ f32x16 frag_mma(const typename MathFrag<MT>::type& a,
                                            const typename MathFrag<MT>::type& b, f32x16 c) {
   if constexpr (MT == kMathX6) return mfma_x6(a, b, c);
   else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// One LDS stage of fp32 operands through mfma_x6 (same operand reads as mfma_stage_bf16).
-template <int BK, int TM, int TN, int LDA_S, int LDB_S, typename F>
-__device__ __forceinline__ void mfma_stage_x6(const float* As, const float* Bs,
-                                              int wm, int wn, int lane, f32x16 (&acc)[TM][TN], F&& mid) {
-  const int l32 = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int kk = 0; kk < BK / 16; ++kk) {
-    Split3 av[TM], bv[TN];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int kr = kk * 16 + 8 * h + j;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) split3_set(av[i], j, As[kr * LDA_S + wm + i * 32 + l32]);
-#pragma unroll
-      for (int t = 0; t < TN; ++t) split3_set(bv[t], j, Bs[kr * LDB_S + wn + t * 32 + l32]);
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int t = 0; t < TN; ++t) acc[i][t] = mfma_x6(av[i], bv[t], acc[i][t]);
-    if (kk == 0) mid();
-  }
 }
 
 // The fwd-form A operand [ks*16 + k][lda] fp32 split into its three bf16 terms, laid out for
@@ -543,10 +501,10 @@ __device__ __forceinline__ void mfma_stage_h1p(const float* As, const float* Bs,
 // f16x3 / fp16 stage with the B operand in registers (fwd_sk_body's BD form, r03): braw = this lane's
 // 8 image values B[k = 8h .. 8h+7][n = its pixel] of the K-step, loaded from global memory a few
 // K-steps ahead; A fragments from the LDS ring as in mfma_stage_h3p.  One K-step, one 32-pixel column
-// per wave (1 x 4 waves).  xf(j, v) maps a loaded value to the scaled operand (v * sB).
-template <int TM, int BM, bool HI_ONLY, typename F, typename X>
+// per wave (1 x 4 waves).  The loaded values are scaled by sB as they are split / rounded.
+template <int TM, int BM, bool HI_ONLY, typename F>
 __device__ __forceinline__ void mfma_stage_hd(const float* As, int wm, int lane, f32x16 (&acc)[TM][1],
-                                              F&& mid, X&& xf, const float (&braw)[8]) {
+                                              F&& mid, float sB, const float (&braw)[8]) {
   const int l32 = lane & 31, h = lane >> 5;
   const f16x8* Ab = reinterpret_cast<const f16x8*>(As);
   if constexpr (HI_ONLY) {
@@ -555,7 +513,7 @@ __device__ __forceinline__ void mfma_stage_hd(const float* As, int wm, int lane,
     for (int i = 0; i < TM; ++i) av[i] = Ab[h * BM + wm + i * 32 + l32];
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) bv[j] = (_Float16)xf(j, braw[j]);
+    for (int j = 0; j < 8; ++j) bv[j] = (_Float16)(braw[j] * sB);
     mfma_prio<kMfmaPrioLds, 1>();
 #pragma unroll
     for (int i = 0; i < TM; ++i) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv, acc[i][0], 0, 0, 0);
@@ -567,12 +525,7 @@ __device__ __forceinline__ void mfma_stage_hd(const float* As, int wm, int lane,
 #pragma unroll
     for (int i = 0; i < TM; ++i) av[i].hi = Ab[h * BM + wm + i * 32 + l32];
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (std::is_same_v<std::decay_t<X>, ScaleXf>) {
-      split2h_scaled(bv, braw, xf.s);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) split2h_set(bv, j, xf(j, braw[j]));
-    }
+    split2h_scaled(bv, braw, sB);
     mfma_prio<kMfmaPrio, 1>();
 #pragma unroll
     for (int i = 0; i < TM; ++i) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i].lo, bv.hi, acc[i][0], 0, 0, 0);
@@ -763,99 +716,6 @@ __global__ void __launch_bounds__(256) k_igemm_fwd(FwdArgs a) {
       }
 }
 
-// Weight gradient: dW[m][n][tap] = sum_p dY[m][p] * X[n][p + shift(tap)], BK pixels per K-step.
-template <int BM, int BN, int BK, int WM, int WN>
-__global__ void __launch_bounds__(256) k_igemm_wgrad(WgradArgs a) {
-  constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
-  static_assert(WM * WN == 4 && TM >= 1 && TN >= 1, "4 waves");
-  static_assert(BK == 32 || BK == 64, "BK");
-  constexpr int LDA_S = BM + 1, LDB_S = BN + 1;  // odd strides: transposing writes are conflict-free
-  constexpr int A_STAGE = BK * LDA_S, STAGE = A_STAGE + BK * LDB_S;
-  __shared__ __attribute__((aligned(16))) float smem[2 * STAGE];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = (wid / WN) * (TM * 32), wn = (wid % WN) * (TN * 32);
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  const int tapz = blockIdx.z % a.ntap;
-  const int split = blockIdx.z / a.ntap;
-  const int br = tapz / a.taps, t = tapz - br * a.taps;
-  const int d = br ? a.dil1 : a.dil0;
-  const int dh = (t / 3 - 1) * d, dw = (t % 3 - 1) * d;
-  const int s_begin = split * a.kps;
-  const int s_end = min(a.ksteps, s_begin + a.kps);
-
-  constexpr int RSTEP = 256 / BK;  // rows covered per pass
-  const int kl = tid % BK, r0 = tid / BK;
-  constexpr int APASS = BM / RSTEP, BPASS = BN / RSTEP;
-  float ra[APASS], rb[BPASS];
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  auto gload = [&](int s) {
-    const int p = s * BK + kl;
-    const bool pv = p < a.P;
-    const int pq = p / a.W, px = p - pq * a.W, py = pq % a.H;
-    const bool vb = pv && (unsigned)(py + dh) < (unsigned)a.H && (unsigned)(px + dw) < (unsigned)a.W;
-    const int off = p + dh * a.W + dw;
-#pragma unroll
-    for (int j = 0; j < APASS; ++j) {
-      const int m = m0 + r0 + RSTEP * j;
-      ra[j] = (pv && m < a.M) ? a.dy[(long long)m * a.P + p] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < BPASS; ++j) {
-      const int n = n0 + r0 + RSTEP * j;
-      rb[j] = (vb && n < a.N) ? a.x[(long long)n * a.P + off] : 0.f;
-    }
-  };
-  auto sstore = [&](int buf) {
-    float* As = smem + buf * STAGE;
-    float* Bs = As + A_STAGE;
-#pragma unroll
-    for (int j = 0; j < APASS; ++j) As[kl * LDA_S + r0 + RSTEP * j] = ra[j];
-#pragma unroll
-    for (int j = 0; j < BPASS; ++j) Bs[kl * LDB_S + r0 + RSTEP * j] = rb[j];
-  };
-
-  if (s_begin < s_end) {
-    gload(s_begin);
-    sstore(0);
-    __syncthreads();
-    int cur = 0;
-    for (int s = s_begin; s < s_end; ++s) {
-      const bool more = s + 1 < s_end;
-      if (more) gload(s + 1);
-      const float* As = smem + cur * STAGE;
-      mfma_stage<BK, TM, TN, LDA_S, LDB_S>(As, As + A_STAGE, wm, wn, lane, acc);
-      if (more) sstore(cur ^ 1);
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-
-  float* C = a.C + (long long)split * a.slab + (long long)br * a.cbranch;
-  const long long ldc = (long long)a.N * a.taps;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const int n = n0 + wn + j * 32 + (lane & 31);
-        if (m < a.M && n < a.N) {
-          const long long idx = (long long)m * ldc + (long long)n * a.taps + t;
-          C[idx] = a.accumulate ? C[idx] + acc[i][j][r] : acc[i][j][r];
-        }
-      }
-}
-
-
 // ---------------------------------------------------------------------------------------------
 // Forward form with an LDS-DMA ring (buffer_load ... lds): no register staging, STAGES-1 K-steps
 // in flight across raw barriers with counted vmcnt waits.  The dilated halo is zero-filled by
@@ -937,7 +797,6 @@ struct SkArgs {
   int T;           // stream-K iterations: (tiles - tdp) * KS  (T * NW < 2^31, checked by the planner)
   int tdp;         // leading tiles that run data-parallel (a multiple of the grid size)
   int gm;          // m-blocks per tile group (sk_tile): 1 = n fastest
-  unsigned long long* prof;  // diagnostic builds only (fwd_sk_body PROF): per-wave cycle sums per loop phase
 };
 
 __device__ __forceinline__ int sk_start(int w, int T, int NW) { return (int)((unsigned)(w * T) / (unsigned)NW); }
@@ -968,23 +827,10 @@ __device__ __forceinline__ int sk_worker_of(int i, int T, int NW) {
 // LDS-DMA left per K-step is the two A-plane pieces (the 8 dword DMA pieces of B cost ~60 issue cycles
 // each, more than the K-step's 12 MFMAs).  Every wave of the 1 x 4 layout reads its own 32 columns,
 // so nothing is lost by not sharing B through LDS.
-// PROF (diagnostic builds only, scripts/probe_sk.hip; 0 in the library), bit 0: s_memtime stamps around
-// the BD loop's phases, summed per wave into sk.prof[wave][phase]: 0 the wait for the stage's A pieces,
-// 1 the barrier, 2 fragment reads + split + MFMA issue + the next stage's issue, 3 the closing
-// lgkmcnt(0), 4 the epilogue, 5 K-steps.  The stamps' own waits forbid overlaps the real kernel has: read
-// the shares, not the length (cdna_hip_programming.md §7, In-kernel stamps).  Timing-only ablations
-// (wrong results): bit 1 no image-operand loads (opaque zeros), bit 2 no A-plane LDS-DMA, bit 3 no
-// K-step barrier.
-__device__ __forceinline__ unsigned long long sk_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
+// (The r05 probe build of this loop - in-kernel phase stamps and timing-only ablations - is recorded in DESIGN.md
+// and was last held by commit b21cc2a: scripts/probe_sk.hip and this function's PROF argument.)
 template <int BM, int BN, int G, int STAGES, int WM, int WN, bool PW = false, int MT = 0, bool ACC = false,
-          bool BD = false, bool BP = false, int PROF = 0>
+          bool BD = false, bool BP = false>
 __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
   // one stream-K iteration = one LDS stage = G consecutive K-steps (16 channels of one tap each);
   // sk.KS counts stages per tile (a.ksteps / G).  PW: pointwise (one unshifted tap), so a B row
@@ -1001,6 +847,7 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
   constexpr bool H1 = MT == kMathH1P;                                 // fp16: the hi plane only
   constexpr bool H3 = MT == kMathH3P || H1;                           // f16x3: two fp16 planes
   constexpr bool APRE = MT == kMathX6P || H3;  // A from pre-split planes
+  static_assert(APRE || MT == kMathF32 || MT == kMathBf16, "the x6 form reads pre-split weights (kMathX6P)");
   constexpr int NQ = H3 ? 4 : 6;  // (plane, k half) blocks of one pre-split K-step in the pack
   constexpr int NQL = H1 ? 2 : NQ;  // of them staged (fp16 math: plane 0's two halves)
   static_assert(!APRE || BM % 64 == 0, "pre-split A: 64-row DMA pieces");
@@ -1063,27 +910,8 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
     iA = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.ascale[1])));
   }
 
-  // PROF & 16 (timing only): a BN-apply + ReLU of the image operand in the BD split, per-channel
-  // (alpha, beta) from an LDS table (alpha = sB, beta = 0: the identity on a non-negative image)
-  const float* tabp = nullptr;
-  if constexpr ((PROF & 16) != 0) {
-    __shared__ float bn_tab[2 * 2048];
-    for (int c = threadIdx.x; c < a.cimg; c += blockDim.x) {
-      const int cb = c >> 4, hh = (c >> 3) & 1, j = c & 7;
-      bn_tab[((cb * 2 + hh) * 2 + 0) * 8 + j] = sB;
-      bn_tab[((cb * 2 + hh) * 2 + 1) * 8 + j] = 0.f;
-    }
-    __syncthreads();
-    tabp = bn_tab;
-  }
   f32x16 acc[TM][TN];
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};  // PROF: phase cycle sums (wave-uniform)
-  unsigned long long te = 0;
   while (true) {
-    if constexpr (PROF & 1) {
-      if (te) ph[4] += sk_stamp() - te;  // the previous segment's epilogue (piece or output stores)
-      te = 0;
-    }
     int t, k_a, k_b;
     if (dp_t < sk.tdp) {
       t = dp_t;
@@ -1168,11 +996,9 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
     };
     set_tap(c_tap);
     float bdq[4][8 * TN];  // BD: the register ring of B values (K-step i in slot i % 4; 8 per column)
-    float bdv[4];          // PROF & 16: the ring's pixel validity (+inf / 0) and channel blocks
-    int bdc[4];
     // part 1: stage s's A pieces into LDS slot `slot`; part 2: its B operand (ring entry bq, or LDS),
     // advancing the cursor; 3: both
-    auto issue = [&](int s, int slot, float (&bq)[8 * TN], float& bv, int& bc, int part = 3) {
+    auto issue = [&](int s, int slot, float (&bq)[8 * TN], int part = 3) {
       float* As = smem + slot * STAGE;
       float* Bs = As + A_STAGE;
       if (!(part & 1)) {
@@ -1189,8 +1015,7 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
           const int g = inst / (NQL * (BM / 64)), r = inst % (NQL * (BM / 64));
           const int qh = r / (BM / 64), mb = (r % (BM / 64)) * 64;
           const int ks = s * G + g;
-          if constexpr (!(PROF & 4))
-            dma_b128(rx, As + inst * 256, (unsigned)(((ks * NQ + qh) * a.lda + m0 + mb + lane) * 16));
+          dma_b128(rx, As + inst * 256, (unsigned)(((ks * NQ + qh) * a.lda + m0 + mb + lane) * 16));
         }
       } else {
         const unsigned a_base = (unsigned)s * a_stage_bytes;
@@ -1226,17 +1051,9 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
           // drain the queue); an out-of-image pixel's voffset >= 2^31 is out of range whatever the
           // soffset
           const unsigned sb = (unsigned)__builtin_amdgcn_readfirstlane(cb16) * chan_bytes;
-          if constexpr ((PROF & 16) != 0) {
-            bv = vbdh != OOB ? __builtin_inff() : 0.f;
-            bc = __builtin_amdgcn_readfirstlane(c_cb);
-          }
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if constexpr (PROF & 2)
-              asm volatile("v_mov_b32 %0, 0" : "=v"(bq[j]));
-            else
-              bq[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, vbdh, (int)(sb + j * chan_bytes), 0));
-          }
+          for (int j = 0; j < 8; ++j)
+            bq[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, vbdh, (int)(sb + j * chan_bytes), 0));
         } else if constexpr (PW) {
           // lanes 0-31 -> row 2*inst, lanes 32-63 -> row 2*inst+1; 4 pixels per lane.  A chunk
           // that straddles P reads the next channel's first pixels: they only reach output
@@ -1281,9 +1098,9 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
       // the compiler's wait-count analysis saw paths with no younger loads and drained the queue -
       // vmcnt(0) - before the split of every first and fourth K-step; r04.  Those drains had also
       // hidden the LDS-DMA ordering race described at the wait below.)
-      issue(k_a, 0, bdq[0], bdv[0], bdc[0]);
-      issue(k_a + 1, 1, bdq[1], bdv[1], bdc[1]);
-      issue(k_a + 2, 2, bdq[2], bdv[2], bdc[2]);
+      issue(k_a, 0, bdq[0]);
+      issue(k_a + 1, 1, bdq[1]);
+      issue(k_a + 2, 2, bdq[2]);
       // K-step i: wait until stage i + 1 landed (only stage i + 2 younger), barrier (stage i + 1 is
       // complete in every wave's LDS pieces, and every wave has read slot i - 1's fragments, at step
       // i - 2), issue stage i + 3 into that slot and ring entry, read + split K-step i + 1's fragments,
@@ -1297,71 +1114,45 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
       // vmcnt(2 * INST_W) - a wave now and then read a stage's A slot before another wave's DMA piece
       // had landed; scripts/dbg_det.py, profiles/r04_bd_wait_race.txt).  The B registers are waited
       // for by the compiler at their use.
-      auto step = [&](int i, float (&cur)[8 * TN], float (&nxt)[8 * TN], float& curv, float& nxtv, int& curc,
-                      int& nxtc) {
-        unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-        if constexpr (PROF & 1) t0 = sk_stamp();
+      auto step = [&](int i, float (&cur)[8 * TN], float (&nxt)[8 * TN]) {
         wait_vmcnt<2 * A_INST_W>();
-        if constexpr (PROF & 1) t1 = sk_stamp();
         // K-step i + 3's B loads right after the wait (their ring entry was read by this wave at i - 1;
         // no other wave is involved), before the barrier: the wait at i + 1 forces all but its four
         // youngest loads, so what it forces was issued a whole K-step earlier rather than after this
         // step's MFMAs.  The A pieces still go after the barrier (their LDS slot is shared).
-        issue(k_a + i + STAGES - 1, 0, nxt, nxtv, nxtc, 2);
-        if constexpr (!(PROF & 8)) __builtin_amdgcn_s_barrier();
-        if constexpr (PROF & 1) t2 = sk_stamp();
+        issue(k_a + i + STAGES - 1, 0, nxt, 2);
+        __builtin_amdgcn_s_barrier();
         const float* As = lds_after_barrier(smem) + (i % STAGES) * STAGE;
-        auto mid = [&] { issue(k_a + i + STAGES - 1, (i + STAGES - 1) % STAGES, nxt, nxtv, nxtc, 1); };
+        auto mid = [&] { issue(k_a + i + STAGES - 1, (i + STAGES - 1) % STAGES, nxt, 1); };
         if constexpr (BP) {
           mfma_stage_hdp<TM, TN, BM, H1>(As, wm, lane, acc, mid, cur);
-        } else if constexpr ((PROF & 16) != 0) {
-          const float4* tq = reinterpret_cast<const float4*>(tabp + (curc * 2 + (lane >> 5)) * 16);
-          const float4 a0 = tq[0], a1 = tq[1], b0 = tq[2], b1 = tq[3];
-          const float al[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-          const float be[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-          const float vm = curv;
-          mfma_stage_hd<TM, BM, H1>(
-              As, wm, lane, acc, mid,
-              [&](int j, float v) { return __builtin_amdgcn_fmed3f(fmaf(v, al[j], be[j]), 0.f, vm); }, cur);
         } else {
-          mfma_stage_hd<TM, BM, H1>(As, wm, lane, acc, mid, ScaleXf{sB}, cur);
+          mfma_stage_hd<TM, BM, H1>(As, wm, lane, acc, mid, sB, cur);
         }
-        if constexpr (PROF & 1) t3 = sk_stamp();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (PROF & 1) {
-          const unsigned long long t4 = sk_stamp();
-          ph[0] += t1 - t0;
-          ph[1] += t2 - t1;
-          ph[2] += t3 - t2;
-          ph[3] += t4 - t3;
-          ph[5] += 1;
-        }
       };
       int i = 0;
       for (; i + 4 <= nst; i += 4) {
-        step(i, bdq[0], bdq[3], bdv[0], bdv[3], bdc[0], bdc[3]);
-        step(i + 1, bdq[1], bdq[0], bdv[1], bdv[0], bdc[1], bdc[0]);
-        step(i + 2, bdq[2], bdq[1], bdv[2], bdv[1], bdc[2], bdc[1]);
-        step(i + 3, bdq[3], bdq[2], bdv[3], bdv[2], bdc[3], bdc[2]);
+        step(i, bdq[0], bdq[3]);
+        step(i + 1, bdq[1], bdq[0]);
+        step(i + 2, bdq[2], bdq[1]);
+        step(i + 3, bdq[3], bdq[2]);
       }
-      if (i < nst) step(i, bdq[0], bdq[3], bdv[0], bdv[3], bdc[0], bdc[3]);
-      if (i + 1 < nst) step(i + 1, bdq[1], bdq[0], bdv[1], bdv[0], bdc[1], bdc[0]);
-      if (i + 2 < nst) step(i + 2, bdq[2], bdq[1], bdv[2], bdv[1], bdc[2], bdc[1]);
+      if (i < nst) step(i, bdq[0], bdq[3]);
+      if (i + 1 < nst) step(i + 1, bdq[1], bdq[0]);
+      if (i + 2 < nst) step(i + 2, bdq[2], bdq[1]);
       wait_vmcnt<0>();  // the stages issued past the end land before the slots are reused
-      if constexpr (PROF & 1) te = sk_stamp();
     } else {
       // as in the BD form: a stage issued every K-step, past the end too, so one wait count
 #pragma unroll
-    for (int k = 0; k < STAGES - 1; ++k) issue(k_a + k, k, bdq[0], bdv[0], bdc[0]);
+    for (int k = 0; k < STAGES - 1; ++k) issue(k_a + k, k, bdq[0]);
     for (int i = 0; i < nst; ++i) {
       wait_vmcnt<(STAGES - 2) * INST_W>();
       __builtin_amdgcn_s_barrier();
       const float* As = lds_after_barrier(smem) + (i % STAGES) * STAGE;
-      auto mid = [&] { issue(k_a + i + STAGES - 1, (i + STAGES - 1) % STAGES, bdq[0], bdv[0], bdc[0]); };
+      auto mid = [&] { issue(k_a + i + STAGES - 1, (i + STAGES - 1) % STAGES, bdq[0]); };
       if constexpr (MT == kMathBf16)
         mfma_stage_bf16<BK, TM, TN, BM, BN>(As, As + A_STAGE, wm, wn, lane, acc, mid);
-      else if constexpr (MT == kMathX6)
-        mfma_stage_x6<BK, TM, TN, BM, BN>(As, As + A_STAGE, wm, wn, lane, acc, mid);
       else if constexpr (MT == kMathX6P)
         mfma_stage_x6p<G, TM, TN, BM, BN>(As, As + A_STAGE, wm, wn, lane, acc, mid);
       else if constexpr (H1)
@@ -1474,13 +1265,6 @@ __device__ __forceinline__ void fwd_sk_body(FwdArgs a, SkArgs sk) {
         }
       }
   }
-  if constexpr (PROF & 1) {
-    if (lane == 0) {  // vector stores of the wave-uniform sums (lane 0)
-      const int gw = blockIdx.x * (blockDim.x >> 6) + wid;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) sk.prof[gw * 8 + k] = ph[k];
-    }
-  }
 }
 
 template <int BM, int BN, int G, int STAGES, int WM, int WN, bool PW = false, int MT = 0, bool ACC = false>
@@ -1491,9 +1275,9 @@ __global__ void __launch_bounds__(256) k_igemm_fwd_sk(FwdArgs a, SkArgs sk) {
 // The same kernel held to two waves per SIMD (<= 256 VGPRs + AGPRs): the f16x3 form, left to the
 // compiler's default budget, takes 199 VGPRs + 64 AGPRs and one wave per SIMD.
 template <int BM, int BN, int G, int STAGES, int WM, int WN, bool PW = false, int MT = 0, bool ACC = false,
-          bool BD = false, bool BP = false, int PROF = 0>
+          bool BD = false, bool BP = false>
 __global__ void __launch_bounds__(256, 2) k_igemm_fwd_sk2(FwdArgs a, SkArgs sk) {
-  fwd_sk_body<BM, BN, G, STAGES, WM, WN, PW, MT, ACC, BD, BP, PROF>(a, sk);
+  fwd_sk_body<BM, BN, G, STAGES, WM, WN, PW, MT, ACC, BD, BP>(a, sk);
 }
 
 // sum of pieces w_lo..w_hi in that order (deterministic), eight loads in flight per step: a tile

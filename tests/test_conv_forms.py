@@ -14,21 +14,6 @@ import pytest
 import conv_form_cases as cf
 from maxsquareloss_amd import hip
 
-# Instantiations no plan chooses, whatever the arguments (built, never launched): the in-loop bf16x6 split
-# (the x6 form reads pre-split weights since r01) and the 64-row tiles on a pre-split image (BP is chosen
-# from M >= 128 only).
-NO_PLAN = {
-    "128.g2.s2.2x2.xy.x6.set.lds", "128.g2.s2.2x2.xy.x6.acc.lds", "128.g1.s3.2x2.xy.x6.set.lds",
-    "128.g1.s3.2x2.xy.x6.acc.lds", "64.g1.s4.1x4.xy.h3p.set.bp", "64.g1.s4.1x4.xy.h3p.acc.bp",
-    "64.g1.s4.1x4.xy.h1p.set.bp", "64.g1.s4.1x4.xy.h1p.acc.bp",
-}
-# Instantiations plan_fwd would choose for arguments no entry point passes: the bf16 entry points take no
-# accumulate flag, and neither does any 3x3 one (the 128-row accumulating tile that is not pointwise).
-NO_ENTRY = {
-    "128.g2.s2.2x2.xy.bf16.acc.lds", "128.g1.s3.2x2.xy.bf16.acc.lds", "64.g2.s2.2x2.xy.bf16.acc.lds",
-    "64.g1.s3.2x2.xy.bf16.acc.lds", "32.g2.s2.1x4.xy.bf16.acc.lds", "128.g1.s4.1x4.xy.h3p.acc.lds",
-    "128.g1.s4.1x4.xy.h1p.acc.lds",
-}
 # The refused calls of the grid (MSL_ERR_SHAPE): the split-K tile kernel (M <= 32 with an odd K-step count)
 # has no bf16 form and no accumulate epilogue.  (family, entry) of every refusal; none runs stream-K.
 REFUSED = {
@@ -54,23 +39,33 @@ def test_every_reachable_kernel_and_schedule_has_a_case(swept):
     print("%d (kernel, schedule) pairs reachable on the grid, all with a case" % len(need))
 
 
-def test_unreached_kernels_are_the_pinned_ones(swept):
+def test_every_built_kernel_is_reached(swept):
+    """The table holds only launchable rows: the grid reaches every one through an entry point."""
     found, _ = swept
     keys = cf.all_form_keys(hip)
     assert len(set(keys)) == len(keys)
-    hit = {k for k, _ in found}
-    assert set(keys) - hit == NO_PLAN | NO_ENTRY
-    # every argument plan_fwd can be given (accumulate on every geometry and family): only NO_PLAN is left
-    raw = set()
+    hit = {k for k, _ in found} - {"tile"}  # ("tile": the split-K tile kernel, no row of the table)
+    assert set(keys) == hit
+    # Every argument plan_fwd can be given (accumulate on every geometry and family).  No entry point passes
+    # accumulate to the bf16 family or to a 3x3 conv; there plan_fwd names a form that is not built - accumulate in
+    # the bf16 math, or on a 128-row f16x3 / fp16 tile that is not pointwise - and the call is refused
+    raw, unbuilt = set(), set()
     for (fam, form), taps, acc, hyb in itertools.product((("fp32", "mfma_f32"), ("fp32", "bf16x6"), ("fp32", "f16x3"),
                                                          ("bf16", "f16x3"), ("fp16", "f16x3")), (9, 1), (0, 1), (1, 0)):
         forms = hip.Forms(cf.F32_FORMS[form], hyb, 1, 1)
         for nb, cimg, m, (n, h, w) in itertools.product((1, 2) if taps == 9 else (1,), cf.GRID_CIMG, cf.GRID_M,
                                                         cf.GRID_PIXELS):
             pl = hip.conv_fwd_plan(cf.FAMILIES[fam], nb, taps, cimg, m, n * h * w, acc, 2 if taps == 9 else 0, forms_=forms)
-            if pl.row >= 0:
+            if not pl.stream_k:  # the split-K tile kernel: test_refusals_are_the_pinned_ones
+                assert pl.row == -1 and pl.status == (cf.MSL_ERR_SHAPE if acc or fam == "bf16" else cf.MSL_OK)
+            elif acc and (fam == "bf16" or (taps == 9 and m > 64 and form == "f16x3")):
+                assert (pl.status, pl.row, pl.stream_k) == (cf.MSL_ERR_SHAPE, -1, 1), (fam, form, taps, cimg, m)
+                unbuilt.add((fam, cf.MATHS[pl.math]))
+            else:
+                assert pl.status == cf.MSL_OK and pl.row >= 0, (fam, form, taps, acc, cimg, m)
                 raw.add(keys[pl.row])
-    assert set(keys) - raw == NO_PLAN
+    assert raw == set(keys)
+    assert unbuilt == {("bf16", "bf16"), ("fp32", "h3p"), ("fp16", "h1p")}
 
 
 def test_refusals_are_the_pinned_ones(swept):
@@ -131,7 +126,7 @@ def test_form_describe_and_bad_arguments():
         assert lib.msl_conv_fwd_form_describe(row, ctypes.addressof(f)) == cf.MSL_OK
         assert f.bm in (32, 64, 128, 256) and f.math in cf.MATHS and f.bform in cf.BFORMS
         seen.add(tuple(getattr(f, name) for name, _ in f._fields_))
-    assert len(seen) == n == len(NO_PLAN) + len(NO_ENTRY) + 39
+    assert len(seen) == n == 39
     for row in (-1, n, n + 1000):
         assert lib.msl_conv_fwd_form_describe(row, ctypes.addressof(f)) == cf.MSL_ERR_ARG
     assert lib.msl_conv_fwd_form_describe(0, None) == cf.MSL_ERR_ARG
