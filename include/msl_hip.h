@@ -406,10 +406,20 @@ int msl_conv_wgrad_plan(int family, int nbranch, int taps, int cin, int cout, in
 
 /* ------------------------------------------------------------------------
  * Bilinear upsample, align_corners=True (F.interpolate at deeplab_multi.py:124,
- * :128).  The forward reproduces torch-CPU's rounding bit for bit.
+ * :128).  The forward reproduces torch-CPU's rounding bit for bit where
+ * ho + wo > 128, the per-axis form torch-CPU takes there (every size a network
+ * runs at); at or below it torch-CPU sums four taps instead and the last bit
+ * can differ: msl_resize_bilinear below has both forms.
  * ---------------------------------------------------------------------- */
 int msl_upsample_fwd(const float* in, float* out, int c, int hi, int wi, int ho, int wo,
                      msl_stream_t stream);
+/* F.interpolate(in, (ho, wo), mode="bilinear", align_corners=True) of an image or mask, c <= 4 planes
+ * [c][hi][wi], up or down, with torch-CPU's rounding bit for bit at every size: where ho + wo > 128 torch
+ * interpolates per axis - msl_upsample_fwd's kernel, launched as it is -, at or below it sums four taps with
+ * rounded weight products (r = w01 v01, then fma of the (0,0), (1,0), (1,1) taps), a form
+ * msl_upsample_fwd does not have.  The evaluator's --scales resizes its network input with this. */
+int msl_resize_bilinear(const float* in, float* out, int c, int hi, int wi, int ho, int wo,
+                        msl_stream_t stream);
 size_t msl_upsample_bwd_workspace(int c, int hi, int wi, int ho, int wo);
 int msl_upsample_bwd(const float* gout, float* gin, int c, int hi, int wi, int ho, int wo,
                      void* ws, size_t ws_bytes, msl_stream_t stream);
@@ -693,6 +703,34 @@ int msl_predict_images(const float* logits, const float* logits_flip, int c, int
                        const uint8_t* id_lut, const uint8_t* palette, const uint8_t* shade,
                        uint8_t* class_out, uint8_t* ids_out, uint8_t* color_out, uint8_t* conf_out,
                        uint8_t* pseudo_out, msl_stream_t stream);
+
+/* Multi-scale / mirror test-time augmentation fused into one launch (--scales, not in the reference).
+ * An entry is the LOW-resolution head output of the image at some input scale, or of that rescaled image's
+ * horizontal mirror (mirror = 1).  Per pixel (y, x) of ho x wo, in fp32 and in the order of the entries:
+ *   acc = sum_k softmax(up_k(logits_k))[y][mirror_k ? wo-1-x : x],   class = np.argmax of acc
+ * (lowest index on ties; a NaN pixel is class 0), up_k the align_corners bilinear upsample of entry k's own
+ * hi x wi to ho x wo with torch-CPU's rounding, as everywhere here.  Two entries (L, 0), (Lf, 1) are
+ * msl_predict_up's --flip rule bit for bit.  The entry array is host memory, read during the call and
+ * passed to the kernel by value: nothing has to outlive the call and a captured graph holds its own copy.
+ * MSL_ERR_ARG before any launch: entries NULL, n outside [1, msl_predict_tta_max_entries()], an entry with
+ * NULL logits, hi < 1, wi < 1 or mirror outside {0, 1}, c outside [1, 32], a size below 1 or
+ * ho * wo >= 2^31, no output at all, label without confusion or the reverse, an image map whose table is
+ * NULL. */
+typedef struct msl_tta_entry {
+  const float* logits; /* [c][hi][wi] on the device */
+  int hi, wi, mirror;
+} msl_tta_entry;
+int msl_predict_tta_max_entries(void); /* 16 */
+/* label / confusion / argmax_out as msl_predict_up. */
+int msl_predict_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, const long long* label,
+                    unsigned long long* confusion, int32_t* argmax_out, msl_stream_t stream);
+/* The same class written as msl_predict_images' five maps from the same tables, four pixels of a row per
+ * thread under the same alignment rule; the winning probability behind conf_out and pseudo_out is
+ * acc[class] / n. */
+int msl_predict_tta_images(const msl_tta_entry* entries, int n, int c, int ho, int wo, const long long* label,
+                           unsigned long long* confusion, float thr, const uint8_t* id_lut,
+                           const uint8_t* palette, const uint8_t* shade, uint8_t* class_out, uint8_t* ids_out,
+                           uint8_t* color_out, uint8_t* conf_out, uint8_t* pseudo_out, msl_stream_t stream);
 
 /* decode_labels (datasets/cityscapes_Dataset.py:352-377) on the device: out[px] = palette[cls[px]] for
  * the npx elements of a class map (int64 when is_int64, else int32), out uint8 [npx*3] HWC RGB, palette a

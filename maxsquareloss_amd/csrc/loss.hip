@@ -573,6 +573,29 @@ __global__ void __launch_bounds__(256) k_upsample_fwd(const float* __restrict__ 
   }
 }
 
+// torch-CPU's other bilinear form.  Where ho + wo <= 128 its CPU kernel does not interpolate per axis:
+// it rounds the four weight products and sums the taps as fma chains starting from the (y0, x1) tap:
+//   w_ab = ly.w_a * lx.w_b;   r = w01 * v01;   r = fma(w00, v00, r);   r = fma(w10, v10, r);   r = fma(w11, v11, r)
+// (the scalar form its fewer-than-a-vector channel counts take: images and masks).  One output per thread:
+// at most 64 x 64 pixels of at most kResizeMaxC planes.
+constexpr int kResizeMaxC = 4;
+__global__ void __launch_bounds__(256) k_resize_four(const float* __restrict__ in, Geo g,
+                                                      float* __restrict__ out) {
+  const int n = g.C * g.Ho * g.Wo;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
+    const int ox = e % g.Wo, r = e / g.Wo;
+    const int oy = r % g.Ho, c = r / g.Ho;
+    const Lin ly = lin(oy, g.sh, g.Hi), lx = lin(ox, g.sw, g.Wi);
+    const float* r0 = in + ((long long)c * g.Hi + ly.i0) * g.Wi;
+    const float* r1 = in + ((long long)c * g.Hi + ly.i1) * g.Wi;
+    float acc = __fmul_rn(__fmul_rn(ly.w0, lx.w1), r0[lx.i1]);
+    acc = __fmaf_rn(__fmul_rn(ly.w0, lx.w0), r0[lx.i0], acc);
+    acc = __fmaf_rn(__fmul_rn(ly.w1, lx.w0), r1[lx.i0], acc);
+    acc = __fmaf_rn(__fmul_rn(ly.w1, lx.w1), r1[lx.i1], acc);
+    out[e] = acc;
+  }
+}
+
 // ---------------------------------------------------------------- prob-input losses
 // record: [0] sum p^2 (MS) | IW: [0..C) class sums, [C..2C) class counts
 template <int IW, int CM>
@@ -1090,6 +1113,170 @@ __global__ void __launch_bounds__(256) k_predict_images(const float* __restrict_
   }
 }
 
+// ---------------------------------------------------------------- evaluation: multi-scale fusion
+// One low-resolution prediction of the image: the head output at some input scale, of the image
+// (mirror 0) or of its horizontal mirror (mirror 1).  sh / sw are make_geo's scales to the output size.
+struct TtaEntry {
+  const float* L;  // [C][Hi][Wi]
+  int Hi, Wi;
+  float sh, sw;
+  int mirror, pad;
+};
+
+constexpr int kTtaMax = 16;
+
+// The table of a call, a kernel argument by value (512 bytes of the kernarg segment: a captured graph
+// holds its own copy).  The entry index is uniform and the entry is read where it lies: no scratch copy.
+struct TtaTable {
+  TtaEntry e[kTtaMax];
+};
+
+// acc = sum over the entries, in their order, of softmax(up(L_k)) at (oy, ox) - at (oy, Wo-1-ox) of a
+// mirrored entry, whose probabilities the reference flips back after upsampling - and the class
+// np.argmax of acc.  0 + p is p, so two entries (L, 0), (Lf, 1) give pixel_class<1>'s p + q: the same
+// class, and acc / 2 its averaged probability.  One entry at a time (unroll 1): the registers are acc and
+// one entry's v, p.
+template <int CM>
+__device__ __forceinline__ int tta_class(const TtaTable& t, int n, int C, int Wo, int oy, int ox,
+                                         float (&acc)[CM]) {
+#pragma unroll
+  for (int c = 0; c < CM; ++c) acc[c] = 0.f;
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) {
+    const TtaEntry e = t.e[k];
+    const Geo g = {C, e.Hi, e.Wi, 0, Wo, e.sh, e.sw};  // up_logits reads C, Hi, Wi
+    const Lin ly = lin(oy, e.sh, e.Hi);
+    const Lin lx = lin(e.mirror ? Wo - 1 - ox : ox, e.sw, e.Wi);
+    float v[CM], p[CM], mx, sum;
+    up_logits<CM>(e.L, g, ly, lx, v);
+    softmax<CM>(v, C, p, mx, sum);
+#pragma unroll
+    for (int c = 0; c < CM; ++c)
+      if (c < C) acc[c] = acc[c] + p[c];
+  }
+  return argmax_np<CM>(acc, C);
+}
+
+// k_predict_up over an entry table: the class of every pixel of Ho x Wo, the optional class map and the
+// confusion matrix by the same LDS histogram and integer atomics.
+template <int CM>
+__global__ void __launch_bounds__(256) k_predict_tta(TtaTable t, int n, int C, int Ho, int Wo,
+                                                      const long long* __restrict__ label,
+                                                      unsigned long long* __restrict__ cm,
+                                                      int32_t* __restrict__ arg) {
+  __shared__ unsigned int h[kMaxC * kMaxC];
+  const int cc = C * C;
+  if (cm) {
+    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
+    __syncthreads();
+  }
+  const long long npx = (long long)Ho * Wo;  // < 2^31 (geo_ok); the stride may step past it
+  for (long long pp = blockIdx.x * 256LL + threadIdx.x; pp < npx; pp += (long long)gridDim.x * 256) {
+    const int px = (int)pp;
+    const int oy = px / Wo, ox = px - oy * Wo;
+    float acc[CM];
+    const int best = tta_class<CM>(t, n, C, Wo, oy, ox, acc);
+    if (arg) arg[px] = best;
+    if (cm) {
+      const long long y = label[px];
+      if (y >= 0 && y < C) atomicAdd(&h[(int)y * C + best], 1u);
+    }
+  }
+  if (cm) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < cc; i += 256)
+      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
+  }
+}
+
+// k_predict_images over an entry table: the same quads, stores and tables; the winning probability is
+// acc at its first maximum divided by n (exact for n = 2: k_predict_images' averaged p).
+template <int CM>
+__global__ void __launch_bounds__(256) k_predict_tta_images(TtaTable t, int n, int C, int Ho, int Wo,
+                                                             const long long* __restrict__ label,
+                                                             unsigned long long* __restrict__ cm, float thr,
+                                                             const uint8_t* __restrict__ id_lut,
+                                                             const uint8_t* __restrict__ palette,
+                                                             const uint8_t* __restrict__ shade, ImgOut o,
+                                                             int vec) {
+  __shared__ unsigned int h[kMaxC * kMaxC];
+  __shared__ unsigned int t_pal[kMaxC], t_id[kMaxC], t_shade[4 * kMaxC];
+  const int cc = C * C;
+  if (cm)
+    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
+  if ((int)threadIdx.x < C) {
+    t_pal[threadIdx.x] = palette ? rgb24(palette, threadIdx.x) : 0u;
+    t_id[threadIdx.x] = id_lut ? id_lut[threadIdx.x] : 0u;
+  }
+  if ((int)threadIdx.x < 4 * C) t_shade[threadIdx.x] = shade ? rgb24(shade, threadIdx.x) : 0u;
+  __syncthreads();
+  const bool want_p = o.conf || o.pseudo;
+  const float fn = (float)n;
+  const int nq = (Wo + 3) >> 2;                   // quads per row
+  const long long nquad = (long long)Ho * nq;     // < 2^31 (geo_ok)
+  for (long long qq = blockIdx.x * 256LL + threadIdx.x; qq < nquad; qq += (long long)gridDim.x * 256) {
+    const int q = (int)qq;
+    const int oy = q / nq, ox0 = (q - oy * nq) << 2;
+    const int row = oy * Wo;
+    unsigned int w_cls = 0u, w_ids = 0u, w_ps = 0u;
+    unsigned int c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u, f0 = 0u, f1 = 0u, f2 = 0u, f3 = 0u;
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int ox = ox0 + j;
+      if (ox >= Wo) break;  // never with vec
+      float acc[CM];
+      const int best = tta_class<CM>(t, n, C, Wo, oy, ox, acc);
+      const int px = row + ox;
+      if (cm) {
+        const long long y = label[px];
+        if (y >= 0 && y < C) atomicAdd(&h[(int)y * C + best], 1u);
+      }
+      unsigned int ps = 255u, cf = 0u;
+      if (want_p) {
+        float top;
+        argmax_first<CM>(acc, C, top);
+        top = top / fn;
+        if (top > thr) ps = (unsigned int)best;
+        const int bucket = top > 0.9f ? 0 : top > 0.8f ? 1 : top > 0.7f ? 2 : top > 0.5f ? 3 : -1;
+        if (bucket >= 0) cf = t_shade[bucket * C + best];
+      }
+      const unsigned int col = t_pal[best], id = t_id[best];
+      if (vec) {
+        const int sh = 8 * j;
+        w_cls |= (unsigned int)best << sh;
+        w_ids |= id << sh;
+        w_ps |= ps << sh;
+        c0 = j == 0 ? col : c0;
+        c1 = j == 1 ? col : c1;
+        c2 = j == 2 ? col : c2;
+        c3 = j == 3 ? col : c3;
+        f0 = j == 0 ? cf : f0;
+        f1 = j == 1 ? cf : f1;
+        f2 = j == 2 ? cf : f2;
+        f3 = j == 3 ? cf : f3;
+      } else {
+        if (o.cls) o.cls[px] = (uint8_t)best;
+        if (o.ids) o.ids[px] = (uint8_t)id;
+        if (o.pseudo) o.pseudo[px] = (uint8_t)ps;
+        if (o.color) store_rgb1(o.color, px, col);
+        if (o.conf) store_rgb1(o.conf, px, cf);
+      }
+    }
+    if (vec) {  // row + ox0 == 4 * q
+      if (o.cls) reinterpret_cast<unsigned int*>(o.cls)[q] = w_cls;
+      if (o.ids) reinterpret_cast<unsigned int*>(o.ids)[q] = w_ids;
+      if (o.pseudo) reinterpret_cast<unsigned int*>(o.pseudo)[q] = w_ps;
+      if (o.color) store_rgb4(o.color, q, c0, c1, c2, c3);
+      if (o.conf) store_rgb4(o.conf, q, f0, f1, f2, f3);
+    }
+  }
+  if (cm) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < cc; i += 256)
+      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
+  }
+}
+
 // decode_labels (datasets/cityscapes_Dataset.py:352-377) on the device: out[px] = palette[cls[px]], black
 // outside [0, C).  A thread takes four pixels: three dword stores with VEC (dword-aligned out), else
 // bytes; the last quad may be partial.
@@ -1281,6 +1468,18 @@ int msl_upsample_fwd(const float* in, float* out, int c, int hi, int wi, int ho,
   const long long n = (long long)c * ho * ((wo + 3) / 4);
   const int blocks = (int)std::min<long long>(cdiv(n, 256), 8192);
   MSL_LAUNCH(k_upsample_fwd, dim3(blocks), dim3(256), 0, as_stream(stream), in, g, out);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_resize_bilinear(const float* in, float* out, int c, int hi, int wi, int ho, int wo,
+                        msl_stream_t stream) {
+  if (c < 1 || c > kResizeMaxC || hi < 1 || wi < 1 || ho < 1 || wo < 1 || !in || !out ||
+      (long long)c * ho * wo >= (1LL << 31))
+    return MSL_ERR_ARG;
+  if ((long long)ho + wo > 128) return msl_upsample_fwd(in, out, c, hi, wi, ho, wo, stream);
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  MSL_LAUNCH(k_resize_four, dim3(cdiv((long long)c * ho * wo, 256)), dim3(256), 0, as_stream(stream), in, g, out);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }
@@ -1488,6 +1687,56 @@ int msl_predict_images(const float* logits, const float* logits_flip, int c, int
     MSL_DISPATCH_C(c, CM,
                    MSL_LAUNCH((k_predict_images<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
                               g, label, confusion, thr, id_lut, palette, shade, o, vec));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_predict_tta_max_entries(void) { return kTtaMax; }
+
+// the caller's entries -> the kernel's table; each entry's scales are make_geo's for its own size
+static bool make_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, TtaTable* t) {
+  if (!entries || n < 1 || n > kTtaMax) return false;
+  *t = TtaTable{};
+  for (int k = 0; k < n; ++k) {
+    const msl_tta_entry& e = entries[k];
+    if (!e.logits || !geo_ok(c, e.hi, e.wi, ho, wo) || (e.mirror != 0 && e.mirror != 1)) return false;
+    const Geo g = make_geo(c, e.hi, e.wi, ho, wo);
+    t->e[k] = {e.logits, e.hi, e.wi, g.sh, g.sw, e.mirror, 0};
+  }
+  return true;
+}
+
+int msl_predict_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, const long long* label,
+                    unsigned long long* confusion, int32_t* argmax_out, msl_stream_t stream) {
+  TtaTable t;
+  if (!geo_ok(c, 1, 1, ho, wo) || !make_tta(entries, n, c, ho, wo, &t) ||
+      (label == nullptr) != (confusion == nullptr) || (!confusion && !argmax_out))
+    return MSL_ERR_ARG;
+  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * wo, 256));
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_predict_tta<CM>), dim3(nblk), dim3(256), 0, as_stream(stream), t, n, c, ho, wo,
+                            label, confusion, argmax_out));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_predict_tta_images(const msl_tta_entry* entries, int n, int c, int ho, int wo, const long long* label,
+                           unsigned long long* confusion, float thr, const uint8_t* id_lut,
+                           const uint8_t* palette, const uint8_t* shade, uint8_t* class_out, uint8_t* ids_out,
+                           uint8_t* color_out, uint8_t* conf_out, uint8_t* pseudo_out, msl_stream_t stream) {
+  TtaTable t;
+  const bool any_out = class_out || ids_out || color_out || conf_out || pseudo_out;
+  if (!geo_ok(c, 1, 1, ho, wo) || !make_tta(entries, n, c, ho, wo, &t) ||
+      (label == nullptr) != (confusion == nullptr) || (!confusion && !any_out) || (ids_out && !id_lut) ||
+      (color_out && !palette) || (conf_out && !shade))
+    return MSL_ERR_ARG;
+  const ImgOut o = {class_out, ids_out, color_out, conf_out, pseudo_out};
+  const int vec = wo % 4 == 0 && dword_aligned(class_out) && dword_aligned(ids_out) &&
+                  dword_aligned(color_out) && dword_aligned(conf_out) && dword_aligned(pseudo_out);
+  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * cdiv(wo, 4), 256));
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_predict_tta_images<CM>), dim3(nblk), dim3(256), 0, as_stream(stream), t, n, c,
+                            ho, wo, label, confusion, thr, id_lut, palette, shade, o, vec));
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

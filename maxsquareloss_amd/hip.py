@@ -155,6 +155,10 @@ SIGNATURES = {
     "msl_style_output_resampled": (c_int, [c_p] + [c_int] * 9 + [c_p] + [c_int] * 6 + [c_f, c_f, c_f, c_p]),
     "msl_label_resize_nearest": (c_int, [c_p, c_int, c_int, c_p, c_int, c_int, c_p]),
     "msl_predict_rectify": (c_int, [c_p, c_p, c_p] + [c_int] * 6 + [c_p, c_p, c_p, c_p]),
+    "msl_resize_bilinear": (c_int, [c_p, c_p] + [c_int] * 5 + [c_p]),
+    "msl_predict_tta_max_entries": (c_int, []),
+    "msl_predict_tta": (c_int, [c_p] + [c_int] * 4 + [c_p, c_p, c_p, c_p]),
+    "msl_predict_tta_images": (c_int, [c_p] + [c_int] * 4 + [c_p, c_p, c_f] + [c_p] * 9),
     "msl_launch_guard_probe": (c_int, [c_int, c_p, c_p]),
     "msl_pconv_dgrad_resmask_sc": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_p, c_p, c_sz, c_p, c_p,
                                            c_int]),
@@ -222,6 +226,11 @@ def ptr(t):
 class Forms(ctypes.Structure):
     """msl_forms (include/msl_hip.h): the kernel forms every conv / pack / BN call takes (ABI 3)."""
     _fields_ = [("f32_form", c_int), ("sk_hybrid", c_int), ("pack_form", c_int), ("bn_fused", c_int)]
+
+
+class TtaEntry(ctypes.Structure):
+    """msl_tta_entry: one low-resolution prediction of msl_predict_tta / msl_predict_tta_images."""
+    _fields_ = [("logits", c_p), ("hi", c_int), ("wi", c_int), ("mirror", c_int)]
 
 
 class JpegComp(ctypes.Structure):

@@ -937,6 +937,18 @@ def upsample_bilinear(x, size):
     return y
 
 
+def resize_bilinear(x, size):
+    """F.interpolate(x, size, mode='bilinear', align_corners=True) of an image (1,C,H,W), C <= 4, up or
+    down, with torch-CPU's rounding at every size (msl_resize_bilinear); no gradient."""
+    x = _check_act(x.detach(), "resize_bilinear")
+    c, hi, wi = x.shape[1:]
+    ho, wo = int(size[0]), int(size[1])
+    y = torch.empty((1, c, ho, wo), dtype=_f32, device=x.device)
+    hip.check(hip.load().msl_resize_bilinear(x.data_ptr(), y.data_ptr(), c, hi, wi, ho, wo, hip.stream_ptr()),
+              "msl_resize_bilinear")
+    return y
+
+
 # --------------------------------------------------------------------------- image pairs
 def pair_join(x_s, x_t):
     """(1,C,H,W) x 2 -> the pair (1,C,2,H,W) ([C][2][H][W]) the trunk ops run as one batch."""
@@ -1237,6 +1249,82 @@ def predict_images(low, out_hw, low_flip=None, label=None, confusion=None, want=
         id_lut.data_ptr(), pal.data_ptr(), shade.data_ptr(), hip.ptr(out.get("class")), hip.ptr(out.get("ids")),
         hip.ptr(out.get("color")), hip.ptr(out.get("confidence")), hip.ptr(out.get("pseudo")), hip.stream_ptr()),
         "msl_predict_images")
+    return out
+
+
+def _tta_table(entries, name):
+    """(msl_tta_entry array, the checked tensors, C) of `entries`: (low (1,C,hi,wi), mirror) pairs, the
+    low-resolution logits of the image at some input scale or - mirror - of that image's horizontal mirror."""
+    entries = list(entries)
+    cap = hip.load().msl_predict_tta_max_entries()
+    if not 1 <= len(entries) <= cap:
+        raise hip.MSLError(f"{name}: {len(entries)} entries; 1 to {cap} are fused in one launch")
+    lows = [_check_act(low.detach(), name) for low, _ in entries]
+    c = lows[0].shape[1]
+    table = (hip.TtaEntry * len(lows))()
+    for k, (low, (_, mirror)) in enumerate(zip(lows, entries)):
+        if low.shape[1] != c or low.device != lows[0].device:
+            raise hip.MSLError(f"{name}: entry {k} has {low.shape[1]} classes on {low.device}, entry 0 {c} on "
+                               f"{lows[0].device}")
+        if mirror not in (0, 1, False, True):
+            raise hip.MSLError(f"{name}: entry {k}'s mirror is {mirror!r}, not 0 or 1")
+        table[k] = hip.TtaEntry(low.data_ptr(), low.shape[2], low.shape[3], int(mirror))
+    return table, lows, c
+
+
+def _tta_label(name, label, confusion, c, ho, wo):
+    if (label is None) != (confusion is None):
+        raise hip.MSLError(f"{name}: label and confusion go together")
+    if label is None:
+        return None
+    label = label.contiguous()
+    if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
+        raise hip.MSLError(f"{name}: label must be a CUDA int64 tensor with {ho * wo} elements")
+    if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
+            not confusion.is_contiguous()):
+        raise hip.MSLError(f"{name}: confusion must be a contiguous CUDA int64 tensor with {c * c} elements")
+    return label
+
+
+def predict_tta(entries, out_hw, label=None, confusion=None, want_argmax=False):
+    """Multi-scale / mirror test-time augmentation in one launch (msl_predict_tta).  `entries`: (low, mirror)
+    pairs, low (1,C,hi,wi) the low-resolution logits of the image at some input scale, mirror 1 when they are
+    those of that image's horizontal mirror; each has its own hi, wi.  The class is np.argmax of the sum, in
+    the entries' order, of softmax(up(low)) - mirrored back where mirror - at out_hw; [(low, 0), (low_flip, 1)]
+    is predict_up's --flip class bit for bit.  label / confusion / want_argmax as predict_up."""
+    table, lows, c = _tta_table(entries, "predict_tta")
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    label = _tta_label("predict_tta", label, confusion, c, ho, wo)
+    if label is None and not want_argmax:
+        raise hip.MSLError("predict_tta: nothing to compute (no label / confusion and want_argmax=False)")
+    arg = torch.empty(ho * wo, dtype=torch.int32, device=lows[0].device) if want_argmax else None
+    hip.check(hip.load().msl_predict_tta(table, len(lows), c, ho, wo, hip.ptr(label), hip.ptr(confusion),
+                                         hip.ptr(arg), hip.stream_ptr()), "msl_predict_tta")
+    return arg
+
+
+def predict_tta_images(entries, out_hw, label=None, confusion=None, want=("color",), thr=0.95, out=None):
+    """predict_tta's class as predict_images' uint8 maps, in the same single launch
+    (msl_predict_tta_images); the probability behind "confidence" and "pseudo" is the summed probability of
+    the class divided by the number of entries.  `want`, `thr`, `out` and the result as predict_images."""
+    table, lows, c = _tta_table(entries, "predict_tta_images")
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    label = _tta_label("predict_tta_images", label, confusion, c, ho, wo)
+    if out is None:
+        out = image_buffers((ho, wo), want, lows[0].device)
+    for k, t in out.items():
+        if (k not in IMAGE_MAPS or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or
+                tuple(t.shape) != (ho, wo) + IMAGE_MAPS[k]):
+            raise hip.MSLError(f"predict_tta_images: output {k!r} must be a contiguous CUDA uint8 tensor of shape "
+                               f"{(ho, wo) + IMAGE_MAPS.get(k, ())}")
+    if not out and label is None:
+        raise hip.MSLError("predict_tta_images: nothing to compute (no map and no label / confusion)")
+    id_lut, pal, shade = image_tables(c, lows[0].device)
+    hip.check(hip.load().msl_predict_tta_images(
+        table, len(lows), c, ho, wo, hip.ptr(label), hip.ptr(confusion), float(thr), id_lut.data_ptr(),
+        pal.data_ptr(), shade.data_ptr(), hip.ptr(out.get("class")), hip.ptr(out.get("ids")),
+        hip.ptr(out.get("color")), hip.ptr(out.get("confidence")), hip.ptr(out.get("pseudo")), hip.stream_ptr()),
+        "msl_predict_tta_images")
     return out
 
 

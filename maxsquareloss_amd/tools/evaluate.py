@@ -10,6 +10,9 @@ What runs where (utils/validate.py): the eval-mode forward under torch.no_grad()
 low-resolution head logits, then one HIP kernel (msl_predict_up) for upsampling, the class and the
 confusion matrix.  --flip (test-time augmentation, evaluate.py:120-135) runs the image and its
 mirror through the trunk as one pair and averages the two softmaxes inside that kernel.
+--scales 0.75,1.0,1.25 (not in the reference) also averages over input scales: each scale's forward - a flip
+pair with --flip - feeds one fusion kernel (msl_predict_tta) that upsamples every low-resolution output
+to the label size and sums the softmaxes (utils/validate.py).
 --graph True replays the per-image work as a captured hipGraph.  Differences from the reference:
 the val set is the val split of --dataset under --data_root_path (datasets/, transformed on the
 device), or without a path synthetic (--val_images items at target_crop_size); batch size 1, at most 500;
@@ -29,7 +32,7 @@ from .. import ops
 from ..utils.synthetic import init_weights
 from ..utils.train_helper import get_model
 from ..utils.images import SUMMARY_EVERY, OutputRequest, parse_save_kinds
-from ..utils.validate import Validator, val_info
+from ..utils.validate import SINGLE_SCALE, Validator, scales_arg, val_info
 from ..datasets import build_loader
 from .train_source import add_train_args, dataset_paths, init_args, str2bool
 
@@ -78,7 +81,7 @@ class Evaluater:
         return Validator(self.model, args.num_classes, (h, w), images, self.device,
                          flip=bool(getattr(args, "flip", False)), graph=bool(getattr(args, "graph", False)),
                          data=self.dataloader.val_loader if self.dataloader else None,
-                         outputs=output_request(args))
+                         outputs=output_request(args), scales=getattr(args, "scales", SINGLE_SCALE))
 
     def main(self):
         self.logger.info("This model will run on %s", torch.cuda.get_device_name(self.device))
@@ -119,6 +122,13 @@ def output_request(args, out_size=None):
                          getattr(args, "data_loader_workers", 0), out_size=out_size, every=every)
 
 
+def add_scales_arg(parser):
+    parser.add_argument("--scales", type=scales_arg, default=SINGLE_SCALE, metavar="S[,S...]",
+                        help="average the softmax over these input scales, each with its mirror under --flip: 1 to 8 "
+                             "values in [0.25, 2.0], e.g. 0.75,1.0,1.25 (default 1.0: off; not in the reference)")
+    return parser
+
+
 def add_save_args(parser):
     a = parser.add_argument
     a("--save_predictions", type=str, default=None, metavar="DIR",
@@ -136,6 +146,7 @@ def build_parser():
                         help="average the softmax of the image and of its horizontal mirror (evaluate.py:120-135)")
     parser.add_argument("--graph", type=str2bool, default=False,
                         help="replay each image after the first as one captured hipGraph (not in the reference)")
+    add_scales_arg(parser)
     add_save_args(parser)
     parser.add_argument("--image_summary", type=str2bool, default=False,
                         help="the reference's image summaries as files: --save_predictions <save_dir>/images for "

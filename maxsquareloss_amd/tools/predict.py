@@ -9,7 +9,9 @@
 Pillow).  Per image: the eval-mode forward down to the low-resolution logits, then one kernel
 (msl_predict_images) that upsamples, takes the class - with --flip of the averaged softmaxes - and writes
 it as the --save_kinds maps; PNG encoding overlaps the next image.  --graph True replays that body as a
-captured hipGraph.  --out_size W,H (not in the reference) upsamples the low-resolution logits straight to
+captured hipGraph.  --scales 0.5,1.0 (not in the reference) averages the softmax over those input scales as
+tools/evaluate.py does, in one fusion kernel (msl_predict_tta_images) that upsamples every scale's output
+straight to the size written.  --out_size W,H (not in the reference) upsamples the low-resolution logits straight to
 that size - 2048,1024 for a Cityscapes submission - instead of the input's; it exists only here, where no
 label has to match.  Without --list_path the tool runs on --val_images (or --synthetic_images) synthetic
 items at target_crop_size, like every other tool, and names the files by index.
@@ -20,8 +22,8 @@ import logging
 from ..datasets import Client_dataset, DeviceLoader
 from ..hip import MSLError
 from ..utils.images import parse_size
-from ..utils.validate import Validator
-from .evaluate import Evaluater, add_save_args, output_request
+from ..utils.validate import SINGLE_SCALE, Validator
+from .evaluate import Evaluater, add_save_args, add_scales_arg, output_request
 from .train_source import add_train_args, init_args, str2bool
 
 
@@ -37,7 +39,8 @@ class Predictor(Evaluater):
             self.dataloader = DeviceLoader(Client_dataset({"list_path": args.list_path}, args), shuffle=False,
                                            workers=getattr(args, "data_loader_workers", 0), seed=args.seed)
         return Validator(self.model, args.num_classes, (h, w), images, self.device, flip=bool(args.flip),
-                         graph=bool(args.graph), data=self.dataloader, outputs=outputs, labelled=False)
+                         graph=bool(args.graph), data=self.dataloader, outputs=outputs, labelled=False,
+                         scales=getattr(args, "scales", SINGLE_SCALE))
 
     def main(self):
         self.validator.run()
@@ -53,6 +56,7 @@ def build_parser():
                         help="average the softmax of the image and of its horizontal mirror")
     parser.add_argument("--graph", type=str2bool, default=False,
                         help="replay each image after the first as one captured hipGraph")
+    add_scales_arg(parser)
     add_save_args(parser)
     parser.add_argument("--out_size", type=parse_size, default=None, metavar="W,H",
                         help="upsample the prediction to this size instead of the input's")

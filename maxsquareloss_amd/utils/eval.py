@@ -83,6 +83,28 @@ class Eval:
         else:
             ops.predict_up(low, out_hw, low_flip, gt, self._dev)
 
+    def add_batch_tta(self, gt_image, entries, out_hw, images=None, thr=0.95):
+        """add_batch_low over several low-resolution predictions of one image, fused in one launch
+        (ops.predict_tta): `entries` are (low, mirror) pairs, each low (1,C,hi,wi) at its own size - the
+        image at some input scale, or that image's mirror.  `images` as add_batch_low
+        (ops.predict_tta_images)."""
+        entries = list(entries)
+        low = entries[0][0] if entries else None
+        if not (torch.is_tensor(low) and low.is_cuda and low.dim() == 4 and low.size(0) == 1):
+            raise hip.MSLError("Eval.add_batch_tta: expects (device logits [1, C, hi, wi], mirror) entries")
+        c = low.size(1)
+        if c != self.num_class:
+            raise hip.MSLError(f"Eval.add_batch_tta: {c} classes, Eval built for {self.num_class}")
+        gt = gt_image.to(device=low.device, dtype=torch.int64).reshape(-1).contiguous()
+        if gt.numel() != int(out_hw[0]) * int(out_hw[1]):
+            raise hip.MSLError("Eval.add_batch_tta: label and prediction sizes differ")
+        if self._dev is None or self._dev.device != low.device:
+            self._dev = torch.zeros(c * c, dtype=torch.int64, device=low.device)
+        if images is not None:
+            ops.predict_tta_images(entries, out_hw, gt, self._dev, out=images, thr=thr)
+        else:
+            ops.predict_tta(entries, out_hw, gt, self._dev)
+
     def add_batch_rectified(self, gt_image, low, crop0, crop1, out_hw, segy0):
         """add_batch_low without flip, followed by the reference's Trainer.rectification with the logits of
         its two stylised, magnified crops, in the same launch (ops.predict_rectify)."""

@@ -17,26 +17,106 @@ With an output request (utils/images.py OutputRequest) the one kernel is ops.pre
 the same class and matrix, and the class written as the requested uint8 maps - static buffers in graph
 mode - which an ImageWriter copies to pinned host slots and encodes as PNGs on host threads while the
 next image runs.  An item's label may then be None (tools/predict.py: nothing to count).
+
+`scales` other than (1.0,) (--scales, not in the reference) is multi-scale test-time augmentation: per
+scale s the input is resized on the device to size_at(H, s) x size_at(W, s) (ops.resize_bilinear,
+align_corners=True with torch-CPU's rounding; the scale that keeps the size takes the input as it is) and
+run through predict_low - as a flip pair with --flip -, and ONE kernel (ops.predict_tta /
+ops.predict_tta_images) upsamples every low-resolution output to the prediction size, sums the softmaxes in
+the scales' order, each mirrored one mirrored back, and takes the class.  In graph mode the resizes, the
+forwards and that launch are one captured graph.  (1.0,) is the single-scale path above, untouched.
 """
+import argparse
 import gc
+import math
 import os
 
 import torch
 
 from .. import ops
-from ..hip import MSLError
+from ..hip import MSLError, load
 from .eval import Eval
 from .images import KIND_MAP, ImageWriter, recover_input
 from .synthetic import SyntheticDomain
 
 VAL_OFFSET = 900          # the val items' seed offset (train: 0, UDA target: 500)
 VAL_ITER_MAX = 500        # evaluate.py:83: valid_iterations = min(num_iterations, 500)
+SINGLE_SCALE = (1.0,)     # --scales' default: no multi-scale fusion
+MAX_SCALES, MIN_SCALE, MAX_SCALE = 8, 0.25, 2.0
 
 
-def predict_image(model, ev, x, y, hw, flip, images=None, thr=0.95):
+def size_at(n, s):
+    """The side n at input scale s: round half up, at least 1 (Python floats)."""
+    return max(1, int(math.floor(n * s + 0.5)))
+
+
+def parse_scales(value, flip=False):
+    """--scales: '0.75,1.0,1.25' or a sequence of numbers -> a tuple of floats, in the order given.  1 to 8
+    values, each in [0.25, 2.0], no duplicates, and with `flip` twice as many entries as scales, at most
+    what one fusion launch takes (msl_predict_tta_max_entries).  Anything else is an MSLError naming the
+    value."""
+    parts = [v.strip() for v in value.split(",")] if isinstance(value, str) else list(value)
+    if not 1 <= len(parts) <= MAX_SCALES:
+        raise MSLError(f"--scales takes 1 to {MAX_SCALES} values, got {len(parts)}: {value!r}")
+    scales = []
+    for v in parts:
+        try:
+            s = float(v)
+        except (TypeError, ValueError):
+            raise MSLError(f"--scales: {v!r} is not a number") from None
+        if not MIN_SCALE <= s <= MAX_SCALE:  # a NaN fails both comparisons
+            raise MSLError(f"--scales: {v!r} is outside [{MIN_SCALE}, {MAX_SCALE}]")
+        if s in scales:
+            raise MSLError(f"--scales: {v!r} is given twice")
+        scales.append(s)
+    if tuple(scales) != SINGLE_SCALE:  # the default takes no fusion launch
+        n, cap = len(scales) * (2 if flip else 1), load(require_gpu=False).msl_predict_tta_max_entries()
+        if n > cap:
+            raise MSLError(f"--scales: {len(scales)} scales{' with --flip' if flip else ''} are {n} predictions, "
+                           f"one launch fuses at most {cap}: {value!r}")
+    return tuple(scales)
+
+
+def scales_arg(text):
+    """parse_scales as an argparse type: its refusals become argparse errors."""
+    try:
+        return parse_scales(text)
+    except MSLError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def tta_entries(model, x, scales, flip):
+    """The (low, mirror) entries of ops.predict_tta for x (1,3,H,W): per scale the resized input's
+    low-resolution logits, followed with `flip` by those of its mirror (one image pair per scale)."""
+    h, w = int(x.shape[-2]), int(x.shape[-1])
+    entries = []
+    for s in scales:
+        hs, ws = size_at(h, s), size_at(w, s)
+        xs = x if (hs, ws) == (h, w) else ops.resize_bilinear(x, (hs, ws))
+        if flip:
+            (low, _), (low_f, _) = model.predict_low(xs, flip=True)
+            entries += [(low, 0), (low_f, 1)]
+        else:
+            entries.append((model.predict_low(xs)[0], 0))
+    return entries
+
+
+def predict_image(model, ev, x, y, hw, flip, images=None, thr=0.95, scales=SINGLE_SCALE):
     """One image into ev's matrix: x (1,3,H,W) fp32, y int64 (H*W labels), both on the device; hw is
     the size the prediction is upsampled to.  `images` (ops.image_buffers) also receives the prediction
-    as uint8 maps, in the same launch; with them y may be None (an unlabelled image: no matrix)."""
+    as uint8 maps, in the same launch; with them y may be None (an unlabelled image: no matrix).
+    `scales` other than (1.0,): the multi-scale fusion of the module text."""
+    if tuple(scales) != SINGLE_SCALE:
+        if y is None and not images:
+            if images is None:
+                raise MSLError("predict_image: an unlabelled image and no output request - nothing to compute")
+            return
+        entries = tta_entries(model, x, scales, flip)
+        if y is not None:
+            ev.add_batch_tta(y, entries, hw, images=images, thr=thr)
+        else:
+            ops.predict_tta_images(entries, hw, out=images, thr=thr)
+        return
     low_f = None
     if flip:
         (low, _), (low_f, _) = model.predict_low(x, flip=True)
@@ -58,10 +138,12 @@ class GraphedPredict:
     (ops.PackCache, rewritten in place) and not the conv weights: before a replay, if any parameter's
     version differs from the versions the packs were built at, they are rebuilt eagerly first."""
 
-    def __init__(self, model, ev, hw, flip, device, maps=None, thr=0.95):
+    def __init__(self, model, ev, hw, flip, device, maps=None, thr=0.95, scales=SINGLE_SCALE):
         """`maps`: the ops.predict_images maps to write on every call, into the static buffers
-        self.images (valid after the call, until the next one)."""
+        self.images (valid after the call, until the next one).  `scales`: predict_image's; the input
+        resizes, every scale's forward and the fusion launch are then this one graph."""
         self.model, self.ev, self.hw, self.flip, self.device = model, ev, hw, flip, device
+        self.scales = tuple(scales)
         self.images = None if maps is None else ops.image_buffers(hw, maps, device)
         self.thr = thr
         self.stream = torch.cuda.Stream(device=device)
@@ -115,7 +197,8 @@ class GraphedPredict:
 
 
     def _body(self):
-        predict_image(self.model, self.ev, self.x, self.y, self.hw, self.flip, self.images, self.thr)
+        predict_image(self.model, self.ev, self.x, self.y, self.hw, self.flip, self.images, self.thr,
+                      self.scales)
 
 
 def val_info(ev, logger, epoch, name=""):
@@ -137,13 +220,15 @@ def val_info(ev, logger, epoch, name=""):
 
 class Validator:
     def __init__(self, model, num_classes, hw, images, device, flip=False, graph=False, rank=0, data=None,
-                 outputs=None, labelled=True):
+                 outputs=None, labelled=True, scales=SINGLE_SCALE):
         """`data`: any iterable of (image (1,3,H,W), label, id) items with a length - a file-backed val
         loader (datasets/), a list of tensors; None = `images` synthetic items of size hw.  `outputs`: an
         OutputRequest (utils/images.py) - the selected items' predictions are also written as PNGs.  Its
         out_size upsamples to another size than the input's, so it needs `labelled=False`: the items'
-        labels are then ignored and no matrix is filled."""
+        labels are then ignored and no matrix is filled.  `scales`: the input scales whose predictions are
+        fused (parse_scales' rules; with `flip` each scale also runs mirrored); (1.0,) = none."""
         self.model, self.hw, self.device, self.flip, self.use_graph = model, (int(hw[0]), int(hw[1])), device, flip, graph
+        self.scales = parse_scales(scales, flip)
         self.outputs, self.labelled = outputs, bool(labelled)
         if outputs is not None and outputs.out_size is not None and self.labelled:
             raise MSLError("--out_size upsamples the prediction to a size no label has: it is for unlabelled "
@@ -155,8 +240,9 @@ class Validator:
             data = SyntheticDomain(self.hw[0], self.hw[1], num_classes, images, rank=rank, offset=VAL_OFFSET)
         self.data = data
         self.valid_iterations = min(len(self.data), VAL_ITER_MAX)
-        # flip [, image size when it is not hw] [, the output size, maps, threshold and whether unlabelled of a
-        # body that writes images] -> GraphedPredict (one capture per body and shape)
+        # flip [, image size when it is not hw] [, the scales when not (1.0,)] [, the output size, maps,
+        # threshold and whether unlabelled of a body that writes images] -> GraphedPredict (one capture per
+        # body and shape)
         self._graphed = {}
 
     def _items(self):
@@ -194,11 +280,13 @@ class Validator:
                     maps, thr = (req.maps, req.threshold) if save else (None, 0.95)
                     if self.use_graph:
                         key = self.flip if size == self.hw else (self.flip, size)
+                        if self.scales != SINGLE_SCALE:
+                            key = (key, "scales", self.scales)
                         if save or y is None:  # another body: its own capture and static output buffers
                             key = (key, hw, maps, thr, y is None)
                         if key not in self._graphed:
                             self._graphed[key] = GraphedPredict(self.model, self.Eval, hw, self.flip, self.device,
-                                                                maps, thr)
+                                                                maps, thr, self.scales)
                         self._graphed[key](x, y)
                         images = self._graphed[key].images
                     else:
@@ -207,7 +295,7 @@ class Validator:
                         predict_image(self.model, self.Eval, x,
                                       None if y is None else y.to(self.device, dtype=torch.long,
                                                                   non_blocking=True).reshape(-1),
-                                      hw, self.flip, images, thr)
+                                      hw, self.flip, images, thr, self.scales)
                     if save:
                         out = {k: images[KIND_MAP[k]] for k in req.kinds if k in KIND_MAP}
                         if "input" in req.kinds:
