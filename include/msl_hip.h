@@ -549,6 +549,44 @@ int msl_iw_maxsquare_prob_fwd(const float* prob, const int64_t* label, int c, in
 int msl_iw_maxsquare_prob_bwd(const float* prob, int c, int hw, const float* weights,
                               const float* gout, float* dprob, msl_stream_t stream);
 
+/* The plan of a fused-loss, upsample or resize call, as a host-only query: no launch, no pointers to data,
+ * usable without a GPU.  It reports what a call of the family does with this geometry through the very
+ * functions the call uses (its refusals, the class-count instantiation, every grid, the row kernel's chunks
+ * and LDS), so it cannot drift from them.  The tests hold every kernel form to fp64 through it
+ * (tests/loss_form_cases.py).  Additive: ABI 3.  Replaces nothing in the reference. */
+#define MSL_LOSS_UP_FWD 0       /* msl_<kind>_up_fwd: k_loss_fwd + k_loss_finalize */
+#define MSL_LOSS_UP_BWD 1       /* msl_<kind>_up_bwd: k_bwd_rows + k_bwd_cols */
+#define MSL_LOSS_UPSAMPLE_BWD 2 /* msl_upsample_bwd: the same two kernels on a given hi-res gradient */
+#define MSL_LOSS_UPSAMPLE_FWD 3 /* msl_upsample_fwd */
+#define MSL_LOSS_RESIZE 4       /* msl_resize_bilinear */
+#define MSL_LOSS_PROB_FWD 5     /* msl_maxsquare_prob_fwd / msl_iw_maxsquare_prob_fwd */
+#define MSL_LOSS_PROB_BWD 6
+#define MSL_LOSS_SOFT_FWD 7     /* msl_soft_ce_fwd / msl_iw_soft_ce_fwd */
+#define MSL_LOSS_SOFT_BWD 8
+#define MSL_LOSS_LABELS 9       /* msl_loss_labels_up / msl_pseudo_labels_up */
+typedef struct msl_loss_plan_info {
+  int status;      /* what the call returns: MSL_OK, MSL_ERR_ARG, MSL_ERR_WORKSPACE or MSL_ERR_SHAPE */
+  int cm;          /* the class-count instantiation: 19, 16, 13, or 32 (the generic body); 0 where the kernels
+                    * take C at run time (msl_upsample_fwd, msl_resize_bilinear) */
+  int fwd_blocks;  /* blocks of the family's flat kernel (256 threads; the forward, or the prob / soft backward) */
+  int fwd_trips;   /* trips of its grid-stride loop (1: every thread takes at most one item) */
+  int rows_chunks; /* k_bwd_rows: column chunks per hi-res row (the grid is ho x rows_chunks) */
+  int per;         /*   low-res columns per chunk */
+  int rows_wmax;   /*   the pixel range its LDS is sized for */
+  int lds_optin;   /*   1: lds_bytes is above 64 KB and the launch opts in to it */
+  int cols_blocks; /* k_bwd_cols: blocks and grid-stride trips */
+  int cols_trips;
+  int vec;         /* k_upsample_fwd stores float4 (wo % 4 == 0), else scalars */
+  int four_tap;    /* msl_resize_bilinear: 1 k_resize_four (ho + wo <= 128), 0 msl_upsample_fwd's kernel */
+  long long lds_bytes;   /* k_bwd_rows: dynamic LDS; above 160 KB the call is MSL_ERR_SHAPE */
+  long long ws_required; /* the workspace bytes the call needs (0: it takes none) */
+} msl_loss_plan_info;
+/* c, hi, wi, ho, wo as the call's; the flat families (prob, soft) take hw = ho * wo and ignore hi, wi.  ws_bytes as
+ * the call's.  The data pointers count as given.  A refused backward still reports rows_chunks .. lds_bytes; every
+ * other field is 0 unless status is MSL_OK.  Returns MSL_ERR_ARG (out untouched) for no out or an unknown family,
+ * else MSL_OK with the call's own status in out. */
+int msl_loss_plan(int family, int c, int hi, int wi, int ho, int wo, size_t ws_bytes, msl_loss_plan_info* out);
+
 /* ------------------------------------------------------------------------
  * BatchNorm2d fused with the Bottleneck's ReLU / residual add (deeplab_multi.py:31-46,
  * :115-117): y = act(bn(x) [+ residual]), act = ReLU if relu else identity.

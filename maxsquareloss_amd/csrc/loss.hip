@@ -1341,13 +1341,129 @@ static size_t t_bytes(int c, int ho, int wi) { return align_up((size_t)c * ho * 
 // pixels whose i0 is one of the chunk's columns or the one before, at most ceil(1/sw) + 1 per
 // column (sw = (Wi-1)/(Wo-1), fp32 as torch computes it), clamped to the row
 static int rows_chunks(const Geo& g) { return std::max(1, std::min(8, g.Wi / 32)); }
+static int rows_per(const Geo& g) { return (g.Wi + rows_chunks(g) - 1) / rows_chunks(g); }  // k_bwd_rows' `per`
 static int rows_wmax(const Geo& g) {
-  const int per = (g.Wi + rows_chunks(g) - 1) / rows_chunks(g);
+  const int per = rows_per(g);
   if (g.Wi < 2 || !(g.sw > 0.f)) return g.Wo;
   const long long each = (long long)std::ceil(1.0 / (double)g.sw) + 2;
   return (int)std::min<long long>(g.Wo, (per + 1) * each);
 }
 static size_t rows_lds(const Geo& g) { return (size_t)rows_wmax(g) * (g.C * 4 + 12); }
+
+constexpr size_t kRowsLdsDefault = 64 * 1024;  // dynamic LDS a kernel gets without opting in
+constexpr size_t kRowsLdsMax = 160 * 1024;     // a gfx950 workgroup's LDS
+
+// A grid-stride launch of 256-thread blocks over n items under a block cap: the blocks, and the
+// trips of the kernel's loop a thread of the first block makes.
+struct Flat {
+  int blocks, trips;
+};
+static Flat flat_launch(long long n, int cap) {
+  Flat f;
+  f.blocks = (int)std::min<long long>((n + 255) / 256, cap);
+  f.trips = (int)((n + (long long)f.blocks * 256 - 1) / ((long long)f.blocks * 256));
+  return f;
+}
+constexpr int kColsBlocks = 2048;     // k_bwd_cols
+constexpr int kFlatBwdBlocks = 4096;  // k_prob_bwd, k_soft_bwd, k_loss_labels, k_pseudo_labels
+constexpr int kUpsampleBlocks = 8192; // k_upsample_fwd
+constexpr int kResizeFourMax = 128;   // msl_resize_bilinear: ho + wo up to here take k_resize_four
+
+// What a call of this file does with its geometry, computed once: every launch below reads its
+// grid, its LDS and its refusals from one of these records and msl_loss_plan reports the same
+// record, so the two cannot drift.  Pointer checks stay with the entry points.
+struct LossPlan {
+  int status;
+  Flat fwd;        // the forward kernel (k_loss_fwd, k_prob_fwd, k_soft_fwd, k_upsample_fwd, k_resize_four,
+                   // the label kernels) or the flat backward (k_prob_bwd, k_soft_bwd)
+  int chunks, per, wmax;  // k_bwd_rows
+  size_t lds;
+  bool optin;      // lds above the default: hipFuncSetAttribute before the launch
+  Flat cols;       // k_bwd_cols
+  bool vec;        // k_upsample_fwd stores float4 (the kernel's own test of Wo)
+  bool four;       // msl_resize_bilinear runs k_resize_four, else msl_upsample_fwd's launch
+  size_t ws_need;
+};
+
+static bool upsample_vec(int wo) { return (wo & 3) == 0; }
+
+static LossPlan refused(LossPlan pl, int status) {
+  pl.status = status;
+  return pl;
+}
+
+// k_loss_fwd + k_loss_finalize
+static LossPlan up_fwd_plan(int c, int hi, int wi, int ho, int wo, size_t ws_bytes) {
+  LossPlan pl = {};
+  if (!geo_ok(c, hi, wi, ho, wo)) return refused(pl, MSL_ERR_ARG);
+  pl.ws_need = part_bytes(c);
+  if (ws_bytes < pl.ws_need) return refused(pl, MSL_ERR_WORKSPACE);
+  pl.fwd = flat_launch((long long)ho * wo, kFwdBlocks);
+  return pl;
+}
+
+// k_bwd_rows + k_bwd_cols (the losses and msl_upsample_bwd)
+static LossPlan up_bwd_plan(int c, int hi, int wi, int ho, int wo, size_t ws_bytes) {
+  LossPlan pl = {};
+  if (!geo_ok(c, hi, wi, ho, wo)) return refused(pl, MSL_ERR_ARG);
+  pl.ws_need = t_bytes(c, ho, wi);
+  if (ws_bytes < pl.ws_need) return refused(pl, MSL_ERR_WORKSPACE);
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  pl.chunks = rows_chunks(g);
+  pl.per = rows_per(g);
+  pl.wmax = rows_wmax(g);
+  pl.lds = rows_lds(g);
+  pl.optin = pl.lds > kRowsLdsDefault;
+  if (pl.lds > kRowsLdsMax) return refused(pl, MSL_ERR_SHAPE);
+  pl.cols = flat_launch((long long)c * hi * wi, kColsBlocks);
+  return pl;
+}
+
+// k_loss_labels / k_pseudo_labels
+static LossPlan labels_plan(int c, int hi, int wi, int ho, int wo) {
+  LossPlan pl = {};
+  if (!geo_ok(c, hi, wi, ho, wo)) return refused(pl, MSL_ERR_ARG);
+  pl.fwd = flat_launch((long long)ho * wo, kFlatBwdBlocks);
+  return pl;
+}
+
+// k_upsample_fwd; max_c: kResizeMaxC through msl_resize_bilinear, else no limit
+static LossPlan upsample_fwd_plan(int c, int hi, int wi, int ho, int wo, int max_c = 0) {
+  LossPlan pl = {};
+  if (c < 1 || (max_c && c > max_c) || hi < 1 || wi < 1 || ho < 1 || wo < 1 || (long long)c * ho * wo >= (1LL << 31))
+    return refused(pl, MSL_ERR_ARG);
+  pl.fwd = flat_launch((long long)c * ho * ((wo + 3) / 4), kUpsampleBlocks);
+  pl.vec = upsample_vec(wo);
+  return pl;
+}
+
+// msl_resize_bilinear: k_resize_four (one output per thread) or msl_upsample_fwd's launch
+static LossPlan resize_plan(int c, int hi, int wi, int ho, int wo) {
+  LossPlan pl = upsample_fwd_plan(c, hi, wi, ho, wo, kResizeMaxC);
+  if (pl.status != MSL_OK || (long long)ho + wo > kResizeFourMax) return pl;
+  pl.four = true;
+  pl.vec = false;
+  pl.fwd.blocks = cdiv((long long)c * ho * wo, 256);
+  pl.fwd.trips = 1;
+  return pl;
+}
+
+// the prob and soft forms on [C][hw]: the forward (partial records, then a finalize) and the backward
+static LossPlan flat_fwd_plan(int c, int hw, size_t ws_bytes) {
+  LossPlan pl = {};
+  if (c < 1 || c > kMaxC || hw < 1) return refused(pl, MSL_ERR_ARG);
+  pl.ws_need = part_bytes(c);
+  if (ws_bytes < pl.ws_need) return refused(pl, MSL_ERR_WORKSPACE);
+  pl.fwd = flat_launch(hw, kFwdBlocks);
+  return pl;
+}
+
+static LossPlan flat_bwd_plan(int c, int hw) {
+  LossPlan pl = {};
+  if (c < 1 || c > kMaxC || hw < 1) return refused(pl, MSL_ERR_ARG);
+  pl.fwd = flat_launch(hw, kFlatBwdBlocks);
+  return pl;
+}
 
 #define MSL_DISPATCH_C(C, CM, ...)      \
   do {                                  \
@@ -1370,13 +1486,14 @@ template <int KIND>
 static int loss_fwd(const float* L1, const float* L2, const int64_t* labels, int c, int hi, int wi,
                     int ho, int wo, float thr, float ratio, float* out, float* stats,
                     int32_t* hist, float* weights, void* ws, size_t ws_bytes, msl_stream_t s) {
-  if (!geo_ok(c, hi, wi, ho, wo) || !L1 || !out || !stats) return MSL_ERR_ARG;
-  if (ws_bytes < part_bytes(c)) return MSL_ERR_WORKSPACE;
+  if (!L1 || !out || !stats) return MSL_ERR_ARG;
+  const LossPlan pl = up_fwd_plan(c, hi, wi, ho, wo, ws_bytes);
+  if (pl.status != MSL_OK) return pl.status;
   const Geo g = make_geo(c, hi, wi, ho, wo);
   hipStream_t st = as_stream(s);
   float* part = (float*)ws;
   const int rec = rec_len(c);
-  const int nblk = std::min(kFwdBlocks, cdiv((long long)ho * wo, 256));
+  const int nblk = pl.fwd.blocks;
   MSL_DISPATCH_C(c, CM,
                  MSL_LAUNCH((k_loss_fwd<KIND, CM>), dim3(nblk), dim3(256), 0, st, L1, L2,
                                     labels, g, thr, part, rec));
@@ -1391,22 +1508,21 @@ template <int KIND>
 static int loss_bwd(const float* L1, const float* L2, const int64_t* labels, const float* gin_hi,
                     int c, int hi, int wi, int ho, int wo, float thr, const float* stats,
                     const float* gout, float* dlow, void* ws, size_t ws_bytes, msl_stream_t s) {
-  if (!geo_ok(c, hi, wi, ho, wo) || !dlow) return MSL_ERR_ARG;
-  if (ws_bytes < t_bytes(c, ho, wi)) return MSL_ERR_WORKSPACE;
+  if (!dlow) return MSL_ERR_ARG;
+  const LossPlan pl = up_bwd_plan(c, hi, wi, ho, wo, ws_bytes);
+  if (pl.status != MSL_OK) return pl.status;
   const Geo g = make_geo(c, hi, wi, ho, wo);
-  const size_t lds = rows_lds(g);
-  if (lds > 160 * 1024) return MSL_ERR_SHAPE;
+  const size_t lds = pl.lds;
   hipStream_t st = as_stream(s);
   float* T = (float*)ws;
   MSL_DISPATCH_C(c, CM, {
     constexpr auto kern = k_bwd_rows<KIND, CM>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    MSL_LAUNCH(kern, dim3(ho, rows_chunks(g)), dim3(256), lds, st, L1, L2, labels, gin_hi, g, thr,
-                       stats, gout, T, rows_wmax(g));
+    if (pl.optin) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    MSL_LAUNCH(kern, dim3(ho, pl.chunks), dim3(256), lds, st, L1, L2, labels, gin_hi, g, thr,
+                       stats, gout, T, pl.wmax);
   });
   MSL_CHECK_LAUNCH();
-  const int n = c * hi * wi;
-  MSL_LAUNCH(k_bwd_cols, dim3(std::min(cdiv(n, 256), 2048)), dim3(256), 0, st,
+  MSL_LAUNCH(k_bwd_cols, dim3(pl.cols.blocks), dim3(256), 0, st,
                      (const float*)T, g, dlow);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
@@ -1416,10 +1532,11 @@ template <int IW>
 static int soft_fwd(const float* inputs, const float* target, int c, int hw, float ignore,
                     float ratio, float* out, float* stats, int32_t* hist, float* weights,
                     void* ws, size_t ws_bytes, msl_stream_t stream) {
-  if (!inputs || !target || !out || !stats || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
-  if (ws_bytes < part_bytes(c)) return MSL_ERR_WORKSPACE;
+  if (!inputs || !target || !out || !stats) return MSL_ERR_ARG;
+  const LossPlan pl = flat_fwd_plan(c, hw, ws_bytes);
+  if (pl.status != MSL_OK) return pl.status;
   hipStream_t st = as_stream(stream);
-  const int nblk = std::min(kFwdBlocks, cdiv(hw, 256));
+  const int nblk = pl.fwd.blocks;
   const int rec = rec_len(c);
   float* part = (float*)ws;
   MSL_DISPATCH_C(c, CM,
@@ -1437,10 +1554,12 @@ template <int IW>
 static int soft_bwd(const float* inputs, const float* target, int c, int hw, float ignore,
                     const float* stats, const float* gout, float* dinputs, float* dtarget,
                     msl_stream_t stream) {
-  if (!inputs || !target || !stats || !gout || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
+  if (!inputs || !target || !stats || !gout) return MSL_ERR_ARG;
+  const LossPlan pl = flat_bwd_plan(c, hw);
+  if (pl.status != MSL_OK) return pl.status;
   if (!dinputs && !dtarget) return MSL_OK;
   MSL_DISPATCH_C(c, CM,
-                 MSL_LAUNCH((k_soft_bwd<IW, CM>), dim3(std::min(cdiv(hw, 256), 4096)),
+                 MSL_LAUNCH((k_soft_bwd<IW, CM>), dim3(pl.fwd.blocks),
                                     dim3(256), 0, as_stream(stream), inputs, target, c, hw,
                                     ignore, stats, gout, dinputs, dtarget));
   MSL_CHECK_LAUNCH();
@@ -1462,24 +1581,23 @@ int msl_loss_stats_elems(void) { return kStats; }
 
 int msl_upsample_fwd(const float* in, float* out, int c, int hi, int wi, int ho, int wo,
                      msl_stream_t stream) {
-  if (c < 1 || hi < 1 || wi < 1 || ho < 1 || wo < 1 || !in || !out || (long long)c * ho * wo >= (1LL << 31))
-    return MSL_ERR_ARG;
+  if (!in || !out) return MSL_ERR_ARG;
+  const LossPlan pl = upsample_fwd_plan(c, hi, wi, ho, wo);
+  if (pl.status != MSL_OK) return pl.status;
   const Geo g = make_geo(c, hi, wi, ho, wo);
-  const long long n = (long long)c * ho * ((wo + 3) / 4);
-  const int blocks = (int)std::min<long long>(cdiv(n, 256), 8192);
-  MSL_LAUNCH(k_upsample_fwd, dim3(blocks), dim3(256), 0, as_stream(stream), in, g, out);
+  MSL_LAUNCH(k_upsample_fwd, dim3(pl.fwd.blocks), dim3(256), 0, as_stream(stream), in, g, out);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }
 
 int msl_resize_bilinear(const float* in, float* out, int c, int hi, int wi, int ho, int wo,
                         msl_stream_t stream) {
-  if (c < 1 || c > kResizeMaxC || hi < 1 || wi < 1 || ho < 1 || wo < 1 || !in || !out ||
-      (long long)c * ho * wo >= (1LL << 31))
-    return MSL_ERR_ARG;
-  if ((long long)ho + wo > 128) return msl_upsample_fwd(in, out, c, hi, wi, ho, wo, stream);
+  if (!in || !out) return MSL_ERR_ARG;
+  const LossPlan pl = resize_plan(c, hi, wi, ho, wo);
+  if (pl.status != MSL_OK) return pl.status;
+  if (!pl.four) return msl_upsample_fwd(in, out, c, hi, wi, ho, wo, stream);
   const Geo g = make_geo(c, hi, wi, ho, wo);
-  MSL_LAUNCH(k_resize_four, dim3(cdiv((long long)c * ho * wo, 256)), dim3(256), 0, as_stream(stream), in, g, out);
+  MSL_LAUNCH(k_resize_four, dim3(pl.fwd.blocks), dim3(256), 0, as_stream(stream), in, g, out);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }
@@ -1558,10 +1676,11 @@ int msl_multi_ce_up_bwd(const float* logits1, const float* logits2, int c, int h
 
 int msl_loss_labels_up(const float* logits1, const float* logits2, int c, int hi, int wi, int ho,
                        int wo, float thr, int32_t* argmax1, int32_t* label2, msl_stream_t stream) {
-  if (!geo_ok(c, hi, wi, ho, wo) || !logits1 || (label2 && !logits2)) return MSL_ERR_ARG;
+  const LossPlan pl = labels_plan(c, hi, wi, ho, wo);
+  if (pl.status != MSL_OK || !logits1 || (label2 && !logits2)) return MSL_ERR_ARG;
   if (!argmax1 && !label2) return MSL_OK;
   const Geo g = make_geo(c, hi, wi, ho, wo);
-  const int nblk = std::min(4096, cdiv((long long)ho * wo, 256));
+  const int nblk = pl.fwd.blocks;
   MSL_DISPATCH_C(c, CM,
                  MSL_LAUNCH((k_loss_labels<CM>), dim3(nblk), dim3(256), 0, as_stream(stream),
                                     logits1, logits2, g, thr, argmax1, label2));
@@ -1615,10 +1734,11 @@ int msl_hard_ce_up_bwd(const float* logits, int c, int hi, int wi, int ho, int w
 
 int msl_pseudo_labels_up(const float* logits, int c, int hi, int wi, int ho, int wo, float thr,
                          int32_t* label, int32_t* argmax_logits, msl_stream_t stream) {
-  if (!geo_ok(c, hi, wi, ho, wo) || !logits) return MSL_ERR_ARG;
+  const LossPlan pl = labels_plan(c, hi, wi, ho, wo);
+  if (pl.status != MSL_OK || !logits) return MSL_ERR_ARG;
   if (!label && !argmax_logits) return MSL_OK;
   const Geo g = make_geo(c, hi, wi, ho, wo);
-  const int nblk = std::min(4096, cdiv((long long)ho * wo, 256));
+  const int nblk = pl.fwd.blocks;
   MSL_DISPATCH_C(c, CM,
                  MSL_LAUNCH((k_pseudo_labels<CM>), dim3(nblk), dim3(256), 0, as_stream(stream),
                                     logits, g, thr, label, argmax_logits));
@@ -1786,10 +1906,11 @@ int msl_iw_soft_ce_bwd(const float* inputs, const float* target, int c, int hw, 
 
 int msl_maxsquare_prob_fwd(const float* prob, int c, int hw, float* out, void* ws,
                            size_t ws_bytes, msl_stream_t stream) {
-  if (!prob || !out || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
-  if (ws_bytes < part_bytes(c)) return MSL_ERR_WORKSPACE;
+  if (!prob || !out) return MSL_ERR_ARG;
+  const LossPlan pl = flat_fwd_plan(c, hw, ws_bytes);
+  if (pl.status != MSL_OK) return pl.status;
   hipStream_t st = as_stream(stream);
-  const int nblk = std::min(kFwdBlocks, cdiv(hw, 256));
+  const int nblk = pl.fwd.blocks;
   const int rec = rec_len(c);
   float* part = (float*)ws;
   MSL_DISPATCH_C(c, CM,
@@ -1806,9 +1927,11 @@ int msl_maxsquare_prob_fwd(const float* prob, int c, int hw, float* out, void* w
 
 int msl_maxsquare_prob_bwd(const float* prob, int c, int hw, const float* gout, float* dprob,
                            msl_stream_t stream) {
-  if (!prob || !gout || !dprob || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
+  if (!prob || !gout || !dprob) return MSL_ERR_ARG;
+  const LossPlan pl = flat_bwd_plan(c, hw);
+  if (pl.status != MSL_OK) return pl.status;
   MSL_DISPATCH_C(c, CM,
-                 MSL_LAUNCH((k_prob_bwd<0, CM>), dim3(std::min(cdiv(hw, 256), 4096)),
+                 MSL_LAUNCH((k_prob_bwd<0, CM>), dim3(pl.fwd.blocks),
                                     dim3(256), 0, as_stream(stream), prob, c, hw,
                                     (const float*)nullptr, gout, dprob));
   MSL_CHECK_LAUNCH();
@@ -1818,10 +1941,11 @@ int msl_maxsquare_prob_bwd(const float* prob, int c, int hw, const float* gout, 
 int msl_iw_maxsquare_prob_fwd(const float* prob, const int64_t* label, int c, int hw,
                               float ratio, float* out, int32_t* hist, float* weights, void* ws,
                               size_t ws_bytes, msl_stream_t stream) {
-  if (!prob || !out || !weights || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
-  if (ws_bytes < part_bytes(c)) return MSL_ERR_WORKSPACE;
+  if (!prob || !out || !weights) return MSL_ERR_ARG;
+  const LossPlan pl = flat_fwd_plan(c, hw, ws_bytes);
+  if (pl.status != MSL_OK) return pl.status;
   hipStream_t st = as_stream(stream);
-  const int nblk = std::min(kFwdBlocks, cdiv(hw, 256));
+  const int nblk = pl.fwd.blocks;
   const int rec = rec_len(c);
   float* part = (float*)ws;
   MSL_DISPATCH_C(c, CM,
@@ -1837,12 +1961,48 @@ int msl_iw_maxsquare_prob_fwd(const float* prob, const int64_t* label, int c, in
 
 int msl_iw_maxsquare_prob_bwd(const float* prob, int c, int hw, const float* weights,
                               const float* gout, float* dprob, msl_stream_t stream) {
-  if (!prob || !weights || !gout || !dprob || c < 1 || c > kMaxC || hw < 1) return MSL_ERR_ARG;
+  if (!prob || !weights || !gout || !dprob) return MSL_ERR_ARG;
+  const LossPlan pl = flat_bwd_plan(c, hw);
+  if (pl.status != MSL_OK) return pl.status;
   MSL_DISPATCH_C(c, CM,
-                 MSL_LAUNCH((k_prob_bwd<1, CM>), dim3(std::min(cdiv(hw, 256), 4096)),
+                 MSL_LAUNCH((k_prob_bwd<1, CM>), dim3(pl.fwd.blocks),
                                     dim3(256), 0, as_stream(stream), prob, c, hw, weights, gout,
                                     dprob));
   MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_loss_plan(int family, int c, int hi, int wi, int ho, int wo, size_t ws_bytes, msl_loss_plan_info* out) {
+  if (!out || family < MSL_LOSS_UP_FWD || family > MSL_LOSS_LABELS) return MSL_ERR_ARG;
+  const long long hw = (long long)ho * wo;  // the flat families' pixel count
+  const bool flat = family >= MSL_LOSS_PROB_FWD && family <= MSL_LOSS_SOFT_BWD;
+  LossPlan pl = {};
+  if (flat && (ho < 1 || wo < 1 || hw >= (1LL << 31))) pl.status = MSL_ERR_ARG;
+  else if (family == MSL_LOSS_UP_FWD) pl = up_fwd_plan(c, hi, wi, ho, wo, ws_bytes);
+  else if (family == MSL_LOSS_UP_BWD || family == MSL_LOSS_UPSAMPLE_BWD) pl = up_bwd_plan(c, hi, wi, ho, wo, ws_bytes);
+  else if (family == MSL_LOSS_UPSAMPLE_FWD) pl = upsample_fwd_plan(c, hi, wi, ho, wo);
+  else if (family == MSL_LOSS_RESIZE) pl = resize_plan(c, hi, wi, ho, wo);
+  else if (family == MSL_LOSS_LABELS) pl = labels_plan(c, hi, wi, ho, wo);
+  else if (family == MSL_LOSS_PROB_FWD || family == MSL_LOSS_SOFT_FWD) pl = flat_fwd_plan(c, (int)hw, ws_bytes);
+  else pl = flat_bwd_plan(c, (int)hw);
+  *out = msl_loss_plan_info{};
+  out->status = pl.status;
+  out->ws_required = (long long)pl.ws_need;
+  // a refused backward still says why: the chunks and the LDS it would have needed
+  out->rows_chunks = pl.chunks;
+  out->per = pl.per;
+  out->rows_wmax = pl.wmax;
+  out->lds_bytes = (long long)pl.lds;
+  out->lds_optin = pl.optin;
+  if (pl.status != MSL_OK) return MSL_OK;
+  const bool by_class = family != MSL_LOSS_UPSAMPLE_FWD && family != MSL_LOSS_RESIZE;
+  if (by_class) MSL_DISPATCH_C(c, CM, out->cm = CM);  // the instantiation the launch's own dispatch picks
+  out->fwd_blocks = pl.fwd.blocks;
+  out->fwd_trips = pl.fwd.trips;
+  out->cols_blocks = pl.cols.blocks;
+  out->cols_trips = pl.cols.trips;
+  out->vec = pl.vec;
+  out->four_tap = pl.four;
   return MSL_OK;
 }
 

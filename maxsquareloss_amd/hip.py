@@ -111,6 +111,7 @@ SIGNATURES = {
     "msl_bn_fwd_mask": (c_int, [c_p] * 10 + [c_int] * 5 + [c_f, c_f, c_int, c_p, c_p, c_sz, c_p, c_p, c_p]),
     "msl_bn_bwd_mask": (c_int, [c_p] * 11 + [c_int] * 6 + [c_p, c_p, c_sz, c_p, c_p]),
     "msl_bn_plan": (c_int, [c_int] * 12 + [c_sz, c_p, c_p]),
+    "msl_loss_plan": (c_int, [c_int] * 6 + [c_sz, c_p]),
     "msl_image_transform": (c_int, [c_p, c_int, c_int, c_int, c_f, c_f, c_f, c_p, c_p]),
     "msl_label_transform": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
     "msl_resize_workspace": (c_sz, [c_int, c_int]),
@@ -303,6 +304,35 @@ def bn_plan(backward, c, p, nimg, training, relu, aligned=1, entry="am", relu_sr
     check(lib.msl_bn_plan(int(backward), c, p, nimg, int(training), int(relu), int(aligned), BN_BWD_ENTRIES[entry],
                           BN_RELU_SOURCES[relu_src], int(has_dx), int(has_absmax), int(has_mask), ws_bytes, fm,
                           ctypes.addressof(out)), "msl_bn_plan")
+    return out
+
+
+class LossPlan(ctypes.Structure):
+    """msl_loss_plan_info: the plan of one fused-loss / upsample / resize call (msl_loss_plan; host only)."""
+    _fields_ = [(n, c_int) for n in ("status", "cm", "fwd_blocks", "fwd_trips", "rows_chunks", "per", "rows_wmax",
+                                     "lds_optin", "cols_blocks", "cols_trips", "vec", "four_tap")] + [
+        ("lds_bytes", c_ll), ("ws_required", c_ll)]
+
+
+LOSS_FAMILIES = {"up_fwd": 0, "up_bwd": 1, "upsample_bwd": 2, "upsample_fwd": 3, "resize": 4, "prob_fwd": 5,
+                 "prob_bwd": 6, "soft_fwd": 7, "soft_bwd": 8, "labels": 9}
+
+
+def loss_plan(family, c, hi, wi, ho, wo, ws_bytes=None):
+    """The plan of a call of `family` (LOSS_FAMILIES) as a LossPlan (no GPU needed); the flat families take
+    ho * wo pixels.  `ws_bytes` defaults to what msl_loss_workspace asks (for msl_upsample_bwd, what
+    msl_upsample_bwd_workspace asks).  The call's own refusal is in .status."""
+    lib = load(require_gpu=False)
+    out = LossPlan()
+    if ws_bytes is None:
+        if family == "upsample_bwd":
+            ws_bytes = lib.msl_upsample_bwd_workspace(c, hi, wi, ho, wo) if min(c, hi, wi, ho, wo) >= 1 else 0
+        elif family.startswith(("prob", "soft")):
+            ws_bytes = lib.msl_loss_workspace(c, 1, 1, 1, ho * wo)
+        else:
+            ws_bytes = lib.msl_loss_workspace(c, hi, wi, ho, wo)
+    check(lib.msl_loss_plan(LOSS_FAMILIES[family], c, hi, wi, ho, wo, ws_bytes, ctypes.addressof(out)),
+          "msl_loss_plan")
     return out
 
 
