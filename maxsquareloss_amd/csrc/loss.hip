@@ -17,14 +17,7 @@
 // is formed in LDS and folded straight into the low-res gradient with the
 // transposed (separable) interpolation weights: rows -> T[C][Ho][Wi] ->
 // d logits[C][Hi][Wi], a fixed-order gather (no atomics).
-#include <math.h>
-#include <cmath>
-
-#include "msl_internal.h"
-
-// No FMA contraction in this file: torch-CPU rounds s*o before subtracting floor(s*o), and
-// the bilinear taps are exact fma(x0, w0, x1*w1) patterns written out explicitly below.
-#pragma clang fp contract(off)
+#include "loss_common.h"  // the pieces shared with predict.hip; no FMA contraction in this file either
 
 namespace msl {
 
@@ -32,82 +25,6 @@ enum LossKind { K_CE = 0, K_MS = 1, K_IW = 2, K_MULTI = 3, K_UPS = 4, K_ENT = 5,
 
 constexpr int kStats = 64;       // floats in a stats record
 constexpr int kFwdBlocks = 1024; // partial records per forward pass
-constexpr int kMaxC = 32;
-
-struct Geo {
-  int C, Hi, Wi, Ho, Wo;
-  float sh, sw;  // align_corners scales (in-1)/(out-1) in fp32, as torch computes them
-};
-
-struct Lin {
-  int i0, i1;
-  float w0, w1;
-};
-
-// area_pixel_compute_source_index + guard_index_and_lambda (align_corners=True)
-__device__ __forceinline__ Lin lin(int o, float s, int n) {
-  const float real = s * (float)o;
-  int i0 = (int)floorf(real);
-  i0 = min(i0, n - 1);
-  const float lam = fminf(fmaxf(real - (float)i0, 0.f), 1.f);
-  Lin r;
-  r.i0 = i0;
-  r.i1 = i0 + (i0 < n - 1 ? 1 : 0);
-  r.w0 = 1.f - lam;
-  r.w1 = lam;
-  return r;
-}
-
-__device__ __forceinline__ float bilerp(const float* __restrict__ plane, int Wi, const Lin& ly,
-                                        const Lin& lx) {
-  const float* r0 = plane + ly.i0 * Wi;
-  const float* r1 = plane + ly.i1 * Wi;
-  const float t0 = __fmaf_rn(r0[lx.i0], lx.w0, __fmul_rn(r0[lx.i1], lx.w1));
-  const float t1 = __fmaf_rn(r1[lx.i0], lx.w0, __fmul_rn(r1[lx.i1], lx.w1));
-  return __fmaf_rn(t0, ly.w0, __fmul_rn(t1, ly.w1));
-}
-
-template <int CM>
-__device__ __forceinline__ void up_logits(const float* __restrict__ L, const Geo& g, const Lin& ly,
-                                          const Lin& lx, float (&v)[CM]) {
-  const int hw = g.Hi * g.Wi;
-#pragma unroll
-  for (int c = 0; c < CM; ++c)
-    if (c < g.C) v[c] = bilerp(L + c * hw, g.Wi, ly, lx);
-}
-
-// softmax over C (max, exp(x - max), sequential sum, divide) + first-max argmax of p
-template <int CM>
-__device__ __forceinline__ void softmax(const float (&v)[CM], int C, float (&p)[CM], float& mx,
-                                        float& sum) {
-  mx = v[0];
-#pragma unroll
-  for (int c = 1; c < CM; ++c)
-    if (c < C) mx = fmaxf(mx, v[c]);
-  sum = 0.f;
-#pragma unroll
-  for (int c = 0; c < CM; ++c)
-    if (c < C) {
-      p[c] = expf(v[c] - mx);
-      sum += p[c];
-    }
-#pragma unroll
-  for (int c = 0; c < CM; ++c)
-    if (c < C) p[c] = p[c] / sum;
-}
-
-template <int CM>
-__device__ __forceinline__ int argmax_first(const float (&p)[CM], int C, float& best) {
-  best = p[0];
-  int a = 0;
-#pragma unroll
-  for (int c = 1; c < CM; ++c)
-    if (c < C && p[c] > best) {
-      best = p[c];
-      a = c;
-    }
-  return a;
-}
 
 // label2 of the multi-level guidance (solve_gta5.py:207-212)
 template <int CM>
@@ -846,488 +763,7 @@ __global__ void __launch_bounds__(256) k_pseudo_labels(const float* __restrict__
   }
 }
 
-// ---------------------------------------------------------------- evaluation: fused prediction
-// np.argmax over the classes (k_confusion's rule, eval.hip): the lowest index wins a tie and a NaN
-// counts as the maximum, so the first NaN is the answer.  Equal to argmax_first when no value is NaN.
-template <int CM>
-__device__ __forceinline__ int argmax_np(const float (&v)[CM], int C) {
-  float best = v[0];
-  int a = 0;
-  bool open = !(best != best);
-#pragma unroll
-  for (int c = 1; c < CM; ++c)
-    if (c < C && open) {
-      if (v[c] != v[c]) {
-        a = c;
-        open = false;
-      } else if (v[c] > best) {
-        best = v[c];
-        a = c;
-      }
-    }
-  return a;
-}
-
-constexpr int kPredictBlocks = 1024;  // grid cap of k_predict_up / k_predict_images (grid-stride beyond it)
-
-// The evaluator's per-pixel decision (tools/evaluate.py:114-141), shared by k_predict_up and
-// k_predict_images.  FLIP = 0: v = up(L) at (ly, ox), the class is np.argmax of v.  FLIP = 1: p =
-// (softmax(up(L))[y][x] + softmax(up(Lf))[y][Wo-1-x]) / 2, Lf the logits of the mirrored image (the
-// reference flips its probabilities back after upsampling), the class is np.argmax of p; v is scratch.
-template <int FLIP, int CM>
-__device__ __forceinline__ int pixel_class(const float* __restrict__ L, const float* __restrict__ Lf,
-                                           const Geo& g, const Lin& ly, int ox, float (&v)[CM],
-                                           float (&p)[CM]) {
-  const Lin lx = lin(ox, g.sw, g.Wi);
-  up_logits<CM>(L, g, ly, lx, v);
-  if (FLIP) {
-    float q[CM], mx, sum;
-    softmax<CM>(v, g.C, p, mx, sum);
-    up_logits<CM>(Lf, g, ly, lin(g.Wo - 1 - ox, g.sw, g.Wi), v);
-    softmax<CM>(v, g.C, q, mx, sum);
-#pragma unroll
-    for (int c = 0; c < CM; ++c)
-      if (c < g.C) p[c] = (p[c] + q[c]) / 2.f;
-    return argmax_np<CM>(p, g.C);
-  }
-  return argmax_np<CM>(v, g.C);
-}
-
-// The class of every hi-res pixel and its (gt, class) cell of the confusion matrix
-// (utils/eval.py:109-115).  The histogram is k_confusion's: per-block LDS counts, integer atomics on the
-// uint64 matrix - exact in any order.  label / cm and arg are nullable (the host requires one of them).
-template <int FLIP, int CM>
-__global__ void __launch_bounds__(256) k_predict_up(const float* __restrict__ L,
-                                                     const float* __restrict__ Lf, Geo g,
-                                                     const long long* __restrict__ label,
-                                                     unsigned long long* __restrict__ cm,
-                                                     int32_t* __restrict__ arg) {
-  __shared__ unsigned int h[kMaxC * kMaxC];
-  const int cc = g.C * g.C;
-  if (cm) {
-    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
-    __syncthreads();
-  }
-  const long long npx = (long long)g.Ho * g.Wo;  // < 2^31 (geo_ok); the stride may step past it
-  for (long long pp = blockIdx.x * 256LL + threadIdx.x; pp < npx; pp += (long long)gridDim.x * 256) {
-    const int px = (int)pp;
-    const int oy = px / g.Wo, ox = px - oy * g.Wo;
-    const Lin ly = lin(oy, g.sh, g.Hi);
-    float v[CM], p[CM];
-    const int best = pixel_class<FLIP, CM>(L, Lf, g, ly, ox, v, p);
-    if (arg) arg[px] = best;
-    if (cm) {
-      const long long y = label[px];
-      if (y >= 0 && y < g.C) atomicAdd(&h[(int)y * g.C + best], 1u);
-    }
-  }
-  if (cm) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < cc; i += 256)
-      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
-  }
-}
-
-// k_predict_up without flip, then the reference's Trainer.rectification (tools/train_source.py:353-381)
-// with both of its crops: inside rows [segy0, segy0 + Ho/2) the pixel (y, x) also has a prediction from
-// crop k = x / (Wo/2), the half-size window magnified, stylised and forwarded on its own, at
-// (2 (y - segy0), 2 (x - k Wo/2)) of its upsampled logits (the reference's nearest x1/2 of that map is
-// [::2, ::2]).  The crop's class replaces the pixel's where its winning logit is strictly greater
-// (numpy's >: a NaN on either side keeps the class).  v is reused for the crop: one pixel's registers.
-template <int CM>
-__global__ void __launch_bounds__(256) k_predict_rectify(const float* __restrict__ L,
-                                                          const float* __restrict__ L0,
-                                                          const float* __restrict__ L1, Geo g, int segy0,
-                                                          const long long* __restrict__ label,
-                                                          unsigned long long* __restrict__ cm,
-                                                          int32_t* __restrict__ arg) {
-  __shared__ unsigned int h[kMaxC * kMaxC];
-  const int cc = g.C * g.C;
-  if (cm) {
-    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
-    __syncthreads();
-  }
-  const int hh = g.Ho >> 1, hw = g.Wo >> 1;
-  const long long npx = (long long)g.Ho * g.Wo;  // < 2^31 (geo_ok); the stride may step past it
-  for (long long pp = blockIdx.x * 256LL + threadIdx.x; pp < npx; pp += (long long)gridDim.x * 256) {
-    const int px = (int)pp;
-    const int oy = px / g.Wo, ox = px - oy * g.Wo;
-    float v[CM];
-    up_logits<CM>(L, g, lin(oy, g.sh, g.Hi), lin(ox, g.sw, g.Wi), v);
-    int best = argmax_np<CM>(v, g.C);
-    if (oy >= segy0 && oy < segy0 + hh) {
-      float m = v[0];  // the value at the class: the maximum, or the first NaN (np.amax)
-#pragma unroll
-      for (int c = 1; c < CM; ++c)
-        if (c == best) m = v[c];
-      const int k = ox >= hw ? 1 : 0;
-      const int yy = 2 * (oy - segy0), xx = 2 * (ox - k * hw);
-      up_logits<CM>(k ? L1 : L0, g, lin(yy, g.sh, g.Hi), lin(xx, g.sw, g.Wi), v);
-      const int nb = argmax_np<CM>(v, g.C);
-      float nm = v[0];
-#pragma unroll
-      for (int c = 1; c < CM; ++c)
-        if (c == nb) nm = v[c];
-      if (nm > m) best = nb;
-    }
-    if (arg) arg[px] = best;
-    if (cm) {
-      const long long y = label[px];
-      if (y >= 0 && y < g.C) atomicAdd(&h[(int)y * g.C + best], 1u);
-    }
-  }
-  if (cm) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < cc; i += 256)
-      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
-  }
-}
-
-// ---------------------------------------------------------------- evaluation: prediction images
-struct ImgOut {
-  uint8_t* cls;     // [Ho*Wo]   the class (k_predict_up's arg as a byte)
-  uint8_t* ids;     // [Ho*Wo]   id_lut[class]
-  uint8_t* color;   // [Ho*Wo*3] palette[class], HWC
-  uint8_t* conf;    // [Ho*Wo*3] shade[bucket of the winning probability][class], black below 0.5
-  uint8_t* pseudo;  // [Ho*Wo]   class where the winning probability > thr, else 255
-};
-
-__device__ __forceinline__ unsigned int rgb24(const uint8_t* __restrict__ t, int i) {
-  return (unsigned int)t[3 * i] | ((unsigned int)t[3 * i + 1] << 8) | ((unsigned int)t[3 * i + 2] << 16);
-}
-
-// four 24-bit pixels -> the three dwords of their 12 bytes
-__device__ __forceinline__ void store_rgb4(uint8_t* __restrict__ out, long long quad, unsigned int a,
-                                           unsigned int b, unsigned int c, unsigned int d) {
-  unsigned int* o = reinterpret_cast<unsigned int*>(out) + 3 * quad;
-  o[0] = a | (b << 24);
-  o[1] = (b >> 8) | (c << 16);
-  o[2] = (c >> 16) | (d << 8);
-}
-
-__device__ __forceinline__ void store_rgb1(uint8_t* __restrict__ out, long long px, unsigned int a) {
-  out[3 * px] = (uint8_t)a;
-  out[3 * px + 1] = (uint8_t)(a >> 8);
-  out[3 * px + 2] = (uint8_t)(a >> 16);
-}
-
-// k_predict_up's decision written as images.  A thread takes four consecutive pixels of one row (a
-// quad), one after the other (the registers are those of one pixel), and keeps their bytes in
-// registers: with VEC (Wo % 4 == 0 and dword-aligned outputs, so quad q is bytes [4q, 4q+4) of a byte
-// map and [12q, 12q+12) of an RGB map) it stores one dword per byte map and three per RGB map; without,
-// rows are not dword-aligned, the last quad of a row is partial and every pixel stores its own bytes.
-// The tables sit in LDS as one dword per entry.  The winning probability is that of argmax_first over
-// p (no flip: softmax(up(L)); flip: the averaged p) and the pseudo-label decision is hard_label's.
-template <int FLIP, int CM>
-__global__ void __launch_bounds__(256) k_predict_images(const float* __restrict__ L,
-                                                         const float* __restrict__ Lf, Geo g,
-                                                         const long long* __restrict__ label,
-                                                         unsigned long long* __restrict__ cm, float thr,
-                                                         const uint8_t* __restrict__ id_lut,
-                                                         const uint8_t* __restrict__ palette,
-                                                         const uint8_t* __restrict__ shade, ImgOut o,
-                                                         int vec) {
-  __shared__ unsigned int h[kMaxC * kMaxC];
-  __shared__ unsigned int t_pal[kMaxC], t_id[kMaxC], t_shade[4 * kMaxC];
-  const int cc = g.C * g.C;
-  if (cm)
-    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
-  if ((int)threadIdx.x < g.C) {
-    t_pal[threadIdx.x] = palette ? rgb24(palette, threadIdx.x) : 0u;
-    t_id[threadIdx.x] = id_lut ? id_lut[threadIdx.x] : 0u;
-  }
-  if ((int)threadIdx.x < 4 * g.C) t_shade[threadIdx.x] = shade ? rgb24(shade, threadIdx.x) : 0u;
-  __syncthreads();
-  const bool want_p = o.conf || o.pseudo;
-  const int nq = (g.Wo + 3) >> 2;                   // quads per row
-  const long long nquad = (long long)g.Ho * nq;     // < 2^31 (geo_ok)
-  for (long long qq = blockIdx.x * 256LL + threadIdx.x; qq < nquad; qq += (long long)gridDim.x * 256) {
-    const int q = (int)qq;
-    const int oy = q / nq, ox0 = (q - oy * nq) << 2;
-    const int row = oy * g.Wo;
-    unsigned int w_cls = 0u, w_ids = 0u, w_ps = 0u;
-    unsigned int c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u, f0 = 0u, f1 = 0u, f2 = 0u, f3 = 0u;
-#pragma unroll 1
-    for (int j = 0; j < 4; ++j) {
-      const int ox = ox0 + j;
-      if (ox >= g.Wo) break;  // never with vec
-      // the row's taps are the same for the four pixels, but hoisted out of the loop they are 2 * CM row
-      // pointers held in VGPRs across it (168 VGPRs at C = 19 against k_predict_up's 45): recompute them
-      // per pixel from a row index the compiler cannot see through
-      int oyj = oy;
-      asm volatile("" : "+v"(oyj));
-      const Lin ly = lin(oyj, g.sh, g.Hi);
-      float v[CM], p[CM];
-      const int best = pixel_class<FLIP, CM>(L, Lf, g, ly, ox, v, p);
-      const int px = row + ox;
-      if (cm) {
-        const long long y = label[px];
-        if (y >= 0 && y < g.C) atomicAdd(&h[(int)y * g.C + best], 1u);
-      }
-      unsigned int ps = 255u, cf = 0u;
-      if (want_p) {
-        if (!FLIP) {
-          float mx, sum;
-          softmax<CM>(v, g.C, p, mx, sum);
-        }
-        float top;
-        argmax_first<CM>(p, g.C, top);
-        if (hard_label<CM>(p, g.C, thr) >= 0) ps = (unsigned int)best;
-        const int bucket = top > 0.9f ? 0 : top > 0.8f ? 1 : top > 0.7f ? 2 : top > 0.5f ? 3 : -1;
-        if (bucket >= 0) cf = t_shade[bucket * g.C + best];
-      }
-      const unsigned int col = t_pal[best], id = t_id[best];
-      if (vec) {
-        const int sh = 8 * j;
-        w_cls |= (unsigned int)best << sh;
-        w_ids |= id << sh;
-        w_ps |= ps << sh;
-        c0 = j == 0 ? col : c0;
-        c1 = j == 1 ? col : c1;
-        c2 = j == 2 ? col : c2;
-        c3 = j == 3 ? col : c3;
-        f0 = j == 0 ? cf : f0;
-        f1 = j == 1 ? cf : f1;
-        f2 = j == 2 ? cf : f2;
-        f3 = j == 3 ? cf : f3;
-      } else {
-        if (o.cls) o.cls[px] = (uint8_t)best;
-        if (o.ids) o.ids[px] = (uint8_t)id;
-        if (o.pseudo) o.pseudo[px] = (uint8_t)ps;
-        if (o.color) store_rgb1(o.color, px, col);
-        if (o.conf) store_rgb1(o.conf, px, cf);
-      }
-    }
-    if (vec) {  // row + ox0 == 4 * q
-      if (o.cls) reinterpret_cast<unsigned int*>(o.cls)[q] = w_cls;
-      if (o.ids) reinterpret_cast<unsigned int*>(o.ids)[q] = w_ids;
-      if (o.pseudo) reinterpret_cast<unsigned int*>(o.pseudo)[q] = w_ps;
-      if (o.color) store_rgb4(o.color, q, c0, c1, c2, c3);
-      if (o.conf) store_rgb4(o.conf, q, f0, f1, f2, f3);
-    }
-  }
-  if (cm) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < cc; i += 256)
-      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
-  }
-}
-
-// ---------------------------------------------------------------- evaluation: multi-scale fusion
-// One low-resolution prediction of the image: the head output at some input scale, of the image
-// (mirror 0) or of its horizontal mirror (mirror 1).  sh / sw are make_geo's scales to the output size.
-struct TtaEntry {
-  const float* L;  // [C][Hi][Wi]
-  int Hi, Wi;
-  float sh, sw;
-  int mirror, pad;
-};
-
-constexpr int kTtaMax = 16;
-
-// The table of a call, a kernel argument by value (512 bytes of the kernarg segment: a captured graph
-// holds its own copy).  The entry index is uniform and the entry is read where it lies: no scratch copy.
-struct TtaTable {
-  TtaEntry e[kTtaMax];
-};
-
-// acc = sum over the entries, in their order, of softmax(up(L_k)) at (oy, ox) - at (oy, Wo-1-ox) of a
-// mirrored entry, whose probabilities the reference flips back after upsampling - and the class
-// np.argmax of acc.  0 + p is p, so two entries (L, 0), (Lf, 1) give pixel_class<1>'s p + q: the same
-// class, and acc / 2 its averaged probability.  One entry at a time (unroll 1): the registers are acc and
-// one entry's v, p.
-template <int CM>
-__device__ __forceinline__ int tta_class(const TtaTable& t, int n, int C, int Wo, int oy, int ox,
-                                         float (&acc)[CM]) {
-#pragma unroll
-  for (int c = 0; c < CM; ++c) acc[c] = 0.f;
-#pragma unroll 1
-  for (int k = 0; k < n; ++k) {
-    const TtaEntry e = t.e[k];
-    const Geo g = {C, e.Hi, e.Wi, 0, Wo, e.sh, e.sw};  // up_logits reads C, Hi, Wi
-    const Lin ly = lin(oy, e.sh, e.Hi);
-    const Lin lx = lin(e.mirror ? Wo - 1 - ox : ox, e.sw, e.Wi);
-    float v[CM], p[CM], mx, sum;
-    up_logits<CM>(e.L, g, ly, lx, v);
-    softmax<CM>(v, C, p, mx, sum);
-#pragma unroll
-    for (int c = 0; c < CM; ++c)
-      if (c < C) acc[c] = acc[c] + p[c];
-  }
-  return argmax_np<CM>(acc, C);
-}
-
-// k_predict_up over an entry table: the class of every pixel of Ho x Wo, the optional class map and the
-// confusion matrix by the same LDS histogram and integer atomics.
-template <int CM>
-__global__ void __launch_bounds__(256) k_predict_tta(TtaTable t, int n, int C, int Ho, int Wo,
-                                                      const long long* __restrict__ label,
-                                                      unsigned long long* __restrict__ cm,
-                                                      int32_t* __restrict__ arg) {
-  __shared__ unsigned int h[kMaxC * kMaxC];
-  const int cc = C * C;
-  if (cm) {
-    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
-    __syncthreads();
-  }
-  const long long npx = (long long)Ho * Wo;  // < 2^31 (geo_ok); the stride may step past it
-  for (long long pp = blockIdx.x * 256LL + threadIdx.x; pp < npx; pp += (long long)gridDim.x * 256) {
-    const int px = (int)pp;
-    const int oy = px / Wo, ox = px - oy * Wo;
-    float acc[CM];
-    const int best = tta_class<CM>(t, n, C, Wo, oy, ox, acc);
-    if (arg) arg[px] = best;
-    if (cm) {
-      const long long y = label[px];
-      if (y >= 0 && y < C) atomicAdd(&h[(int)y * C + best], 1u);
-    }
-  }
-  if (cm) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < cc; i += 256)
-      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
-  }
-}
-
-// k_predict_images over an entry table: the same quads, stores and tables; the winning probability is
-// acc at its first maximum divided by n (exact for n = 2: k_predict_images' averaged p).
-template <int CM>
-__global__ void __launch_bounds__(256) k_predict_tta_images(TtaTable t, int n, int C, int Ho, int Wo,
-                                                             const long long* __restrict__ label,
-                                                             unsigned long long* __restrict__ cm, float thr,
-                                                             const uint8_t* __restrict__ id_lut,
-                                                             const uint8_t* __restrict__ palette,
-                                                             const uint8_t* __restrict__ shade, ImgOut o,
-                                                             int vec) {
-  __shared__ unsigned int h[kMaxC * kMaxC];
-  __shared__ unsigned int t_pal[kMaxC], t_id[kMaxC], t_shade[4 * kMaxC];
-  const int cc = C * C;
-  if (cm)
-    for (int i = threadIdx.x; i < cc; i += 256) h[i] = 0u;
-  if ((int)threadIdx.x < C) {
-    t_pal[threadIdx.x] = palette ? rgb24(palette, threadIdx.x) : 0u;
-    t_id[threadIdx.x] = id_lut ? id_lut[threadIdx.x] : 0u;
-  }
-  if ((int)threadIdx.x < 4 * C) t_shade[threadIdx.x] = shade ? rgb24(shade, threadIdx.x) : 0u;
-  __syncthreads();
-  const bool want_p = o.conf || o.pseudo;
-  const float fn = (float)n;
-  const int nq = (Wo + 3) >> 2;                   // quads per row
-  const long long nquad = (long long)Ho * nq;     // < 2^31 (geo_ok)
-  for (long long qq = blockIdx.x * 256LL + threadIdx.x; qq < nquad; qq += (long long)gridDim.x * 256) {
-    const int q = (int)qq;
-    const int oy = q / nq, ox0 = (q - oy * nq) << 2;
-    const int row = oy * Wo;
-    unsigned int w_cls = 0u, w_ids = 0u, w_ps = 0u;
-    unsigned int c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u, f0 = 0u, f1 = 0u, f2 = 0u, f3 = 0u;
-#pragma unroll 1
-    for (int j = 0; j < 4; ++j) {
-      const int ox = ox0 + j;
-      if (ox >= Wo) break;  // never with vec
-      float acc[CM];
-      const int best = tta_class<CM>(t, n, C, Wo, oy, ox, acc);
-      const int px = row + ox;
-      if (cm) {
-        const long long y = label[px];
-        if (y >= 0 && y < C) atomicAdd(&h[(int)y * C + best], 1u);
-      }
-      unsigned int ps = 255u, cf = 0u;
-      if (want_p) {
-        float top;
-        argmax_first<CM>(acc, C, top);
-        top = top / fn;
-        if (top > thr) ps = (unsigned int)best;
-        const int bucket = top > 0.9f ? 0 : top > 0.8f ? 1 : top > 0.7f ? 2 : top > 0.5f ? 3 : -1;
-        if (bucket >= 0) cf = t_shade[bucket * C + best];
-      }
-      const unsigned int col = t_pal[best], id = t_id[best];
-      if (vec) {
-        const int sh = 8 * j;
-        w_cls |= (unsigned int)best << sh;
-        w_ids |= id << sh;
-        w_ps |= ps << sh;
-        c0 = j == 0 ? col : c0;
-        c1 = j == 1 ? col : c1;
-        c2 = j == 2 ? col : c2;
-        c3 = j == 3 ? col : c3;
-        f0 = j == 0 ? cf : f0;
-        f1 = j == 1 ? cf : f1;
-        f2 = j == 2 ? cf : f2;
-        f3 = j == 3 ? cf : f3;
-      } else {
-        if (o.cls) o.cls[px] = (uint8_t)best;
-        if (o.ids) o.ids[px] = (uint8_t)id;
-        if (o.pseudo) o.pseudo[px] = (uint8_t)ps;
-        if (o.color) store_rgb1(o.color, px, col);
-        if (o.conf) store_rgb1(o.conf, px, cf);
-      }
-    }
-    if (vec) {  // row + ox0 == 4 * q
-      if (o.cls) reinterpret_cast<unsigned int*>(o.cls)[q] = w_cls;
-      if (o.ids) reinterpret_cast<unsigned int*>(o.ids)[q] = w_ids;
-      if (o.pseudo) reinterpret_cast<unsigned int*>(o.pseudo)[q] = w_ps;
-      if (o.color) store_rgb4(o.color, q, c0, c1, c2, c3);
-      if (o.conf) store_rgb4(o.conf, q, f0, f1, f2, f3);
-    }
-  }
-  if (cm) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < cc; i += 256)
-      if (h[i]) atomicAdd(&cm[i], (unsigned long long)h[i]);
-  }
-}
-
-// decode_labels (datasets/cityscapes_Dataset.py:352-377) on the device: out[px] = palette[cls[px]], black
-// outside [0, C).  A thread takes four pixels: three dword stores with VEC (dword-aligned out), else
-// bytes; the last quad may be partial.
-constexpr int kColorizeMaxC = 256;
-template <typename T>
-__global__ void __launch_bounds__(256) k_colorize(const T* __restrict__ cls, long long npx,
-                                                   const uint8_t* __restrict__ palette, int C,
-                                                   uint8_t* __restrict__ out, int vec) {
-  __shared__ unsigned int t_pal[kColorizeMaxC];
-  for (int i = threadIdx.x; i < C; i += 256) t_pal[i] = rgb24(palette, i);
-  __syncthreads();
-  const long long nquad = (npx + 3) >> 2;
-  for (long long q = blockIdx.x * 256LL + threadIdx.x; q < nquad; q += (long long)gridDim.x * 256) {
-    unsigned int col[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long px = 4 * q + j;
-      col[j] = 0u;
-      if (px < npx) {
-        const long long k = (long long)cls[px];
-        if (k >= 0 && k < C) col[j] = t_pal[(int)k];
-      }
-    }
-    if (vec && 4 * q + 3 < npx) {
-      store_rgb4(out, q, col[0], col[1], col[2], col[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (4 * q + j < npx) store_rgb1(out, 4 * q + j, col[j]);
-    }
-  }
-}
-
 // ---------------------------------------------------------------- host helpers
-static bool geo_ok(int c, int hi, int wi, int ho, int wo) {
-  return c >= 1 && c <= kMaxC && hi >= 1 && wi >= 1 && ho >= 1 && wo >= 1 &&
-         (long long)ho * wo < (1LL << 31);
-}
-
-static Geo make_geo(int c, int hi, int wi, int ho, int wo) {
-  Geo g;
-  g.C = c;
-  g.Hi = hi;
-  g.Wi = wi;
-  g.Ho = ho;
-  g.Wo = wo;
-  g.sh = ho > 1 ? (float)(hi - 1) / (float)(ho - 1) : 0.f;
-  g.sw = wo > 1 ? (float)(wi - 1) / (float)(wo - 1) : 0.f;
-  return g;
-}
-
 static int rec_len(int C) { return 2 * C > 2 ? 2 * C : 2; }
 
 // partial records + one trailing stats record (used by the prob-input forms)
@@ -1464,23 +900,6 @@ static LossPlan flat_bwd_plan(int c, int hw) {
   pl.fwd = flat_launch(hw, kFlatBwdBlocks);
   return pl;
 }
-
-#define MSL_DISPATCH_C(C, CM, ...)      \
-  do {                                  \
-    if ((C) == 19) {                    \
-      constexpr int CM = 19;            \
-      __VA_ARGS__;                      \
-    } else if ((C) == 16) {             \
-      constexpr int CM = 16;            \
-      __VA_ARGS__;                      \
-    } else if ((C) == 13) {             \
-      constexpr int CM = 13;            \
-      __VA_ARGS__;                      \
-    } else {                            \
-      constexpr int CM = kMaxC;         \
-      __VA_ARGS__;                      \
-    }                                   \
-  } while (0)
 
 template <int KIND>
 static int loss_fwd(const float* L1, const float* L2, const int64_t* labels, int c, int hi, int wi,
@@ -1742,139 +1161,6 @@ int msl_pseudo_labels_up(const float* logits, int c, int hi, int wi, int ho, int
   MSL_DISPATCH_C(c, CM,
                  MSL_LAUNCH((k_pseudo_labels<CM>), dim3(nblk), dim3(256), 0, as_stream(stream),
                                     logits, g, thr, label, argmax_logits));
-  MSL_CHECK_LAUNCH();
-  return MSL_OK;
-}
-
-int msl_predict_up(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
-                   const long long* label, unsigned long long* confusion, int32_t* argmax_out,
-                   msl_stream_t stream) {
-  if (!geo_ok(c, hi, wi, ho, wo) || !logits || (label == nullptr) != (confusion == nullptr) ||
-      (!confusion && !argmax_out))
-    return MSL_ERR_ARG;
-  const Geo g = make_geo(c, hi, wi, ho, wo);
-  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * wo, 256));
-  hipStream_t st = as_stream(stream);
-  if (logits_flip)
-    MSL_DISPATCH_C(c, CM,
-                   MSL_LAUNCH((k_predict_up<1, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
-                              g, label, confusion, argmax_out));
-  else
-    MSL_DISPATCH_C(c, CM,
-                   MSL_LAUNCH((k_predict_up<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
-                              g, label, confusion, argmax_out));
-  MSL_CHECK_LAUNCH();
-  return MSL_OK;
-}
-
-int msl_predict_rectify(const float* base, const float* crop0, const float* crop1, int c, int hi, int wi, int ho,
-                        int wo, int segy0, const long long* label, unsigned long long* confusion,
-                        int32_t* argmax_out, msl_stream_t stream) {
-  if (!geo_ok(c, hi, wi, ho, wo) || !base || !crop0 || !crop1 || (label == nullptr) != (confusion == nullptr) ||
-      (!confusion && !argmax_out) || (ho & 1) || (wo & 1) || segy0 < 0 || segy0 > ho / 2)
-    return MSL_ERR_ARG;
-  const Geo g = make_geo(c, hi, wi, ho, wo);
-  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * wo, 256));
-  MSL_DISPATCH_C(c, CM,
-                 MSL_LAUNCH((k_predict_rectify<CM>), dim3(nblk), dim3(256), 0, as_stream(stream), base, crop0,
-                            crop1, g, segy0, label, confusion, argmax_out));
-  MSL_CHECK_LAUNCH();
-  return MSL_OK;
-}
-
-static bool dword_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-int msl_predict_images(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
-                       const long long* label, unsigned long long* confusion, float thr,
-                       const uint8_t* id_lut, const uint8_t* palette, const uint8_t* shade,
-                       uint8_t* class_out, uint8_t* ids_out, uint8_t* color_out, uint8_t* conf_out,
-                       uint8_t* pseudo_out, msl_stream_t stream) {
-  const bool any_out = class_out || ids_out || color_out || conf_out || pseudo_out;
-  if (!geo_ok(c, hi, wi, ho, wo) || !logits || (label == nullptr) != (confusion == nullptr) ||
-      (!confusion && !any_out) || (ids_out && !id_lut) || (color_out && !palette) || (conf_out && !shade))
-    return MSL_ERR_ARG;
-  const Geo g = make_geo(c, hi, wi, ho, wo);
-  const ImgOut o = {class_out, ids_out, color_out, conf_out, pseudo_out};
-  const int vec = wo % 4 == 0 && dword_aligned(class_out) && dword_aligned(ids_out) &&
-                  dword_aligned(color_out) && dword_aligned(conf_out) && dword_aligned(pseudo_out);
-  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * cdiv(wo, 4), 256));
-  hipStream_t st = as_stream(stream);
-  if (logits_flip)
-    MSL_DISPATCH_C(c, CM,
-                   MSL_LAUNCH((k_predict_images<1, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
-                              g, label, confusion, thr, id_lut, palette, shade, o, vec));
-  else
-    MSL_DISPATCH_C(c, CM,
-                   MSL_LAUNCH((k_predict_images<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip,
-                              g, label, confusion, thr, id_lut, palette, shade, o, vec));
-  MSL_CHECK_LAUNCH();
-  return MSL_OK;
-}
-
-int msl_predict_tta_max_entries(void) { return kTtaMax; }
-
-// the caller's entries -> the kernel's table; each entry's scales are make_geo's for its own size
-static bool make_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, TtaTable* t) {
-  if (!entries || n < 1 || n > kTtaMax) return false;
-  *t = TtaTable{};
-  for (int k = 0; k < n; ++k) {
-    const msl_tta_entry& e = entries[k];
-    if (!e.logits || !geo_ok(c, e.hi, e.wi, ho, wo) || (e.mirror != 0 && e.mirror != 1)) return false;
-    const Geo g = make_geo(c, e.hi, e.wi, ho, wo);
-    t->e[k] = {e.logits, e.hi, e.wi, g.sh, g.sw, e.mirror, 0};
-  }
-  return true;
-}
-
-int msl_predict_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, const long long* label,
-                    unsigned long long* confusion, int32_t* argmax_out, msl_stream_t stream) {
-  TtaTable t;
-  if (!geo_ok(c, 1, 1, ho, wo) || !make_tta(entries, n, c, ho, wo, &t) ||
-      (label == nullptr) != (confusion == nullptr) || (!confusion && !argmax_out))
-    return MSL_ERR_ARG;
-  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * wo, 256));
-  MSL_DISPATCH_C(c, CM,
-                 MSL_LAUNCH((k_predict_tta<CM>), dim3(nblk), dim3(256), 0, as_stream(stream), t, n, c, ho, wo,
-                            label, confusion, argmax_out));
-  MSL_CHECK_LAUNCH();
-  return MSL_OK;
-}
-
-int msl_predict_tta_images(const msl_tta_entry* entries, int n, int c, int ho, int wo, const long long* label,
-                           unsigned long long* confusion, float thr, const uint8_t* id_lut,
-                           const uint8_t* palette, const uint8_t* shade, uint8_t* class_out, uint8_t* ids_out,
-                           uint8_t* color_out, uint8_t* conf_out, uint8_t* pseudo_out, msl_stream_t stream) {
-  TtaTable t;
-  const bool any_out = class_out || ids_out || color_out || conf_out || pseudo_out;
-  if (!geo_ok(c, 1, 1, ho, wo) || !make_tta(entries, n, c, ho, wo, &t) ||
-      (label == nullptr) != (confusion == nullptr) || (!confusion && !any_out) || (ids_out && !id_lut) ||
-      (color_out && !palette) || (conf_out && !shade))
-    return MSL_ERR_ARG;
-  const ImgOut o = {class_out, ids_out, color_out, conf_out, pseudo_out};
-  const int vec = wo % 4 == 0 && dword_aligned(class_out) && dword_aligned(ids_out) &&
-                  dword_aligned(color_out) && dword_aligned(conf_out) && dword_aligned(pseudo_out);
-  const int nblk = std::min(kPredictBlocks, cdiv((long long)ho * cdiv(wo, 4), 256));
-  MSL_DISPATCH_C(c, CM,
-                 MSL_LAUNCH((k_predict_tta_images<CM>), dim3(nblk), dim3(256), 0, as_stream(stream), t, n, c,
-                            ho, wo, label, confusion, thr, id_lut, palette, shade, o, vec));
-  MSL_CHECK_LAUNCH();
-  return MSL_OK;
-}
-
-int msl_colorize(const void* cls, int is_int64, long long npx, const uint8_t* palette, int c, uint8_t* out,
-                 msl_stream_t stream) {
-  if (!cls || !palette || !out || npx < 0 || c < 1 || c > kColorizeMaxC || (is_int64 != 0 && is_int64 != 1))
-    return MSL_ERR_ARG;
-  if (npx == 0) return MSL_OK;
-  const int vec = dword_aligned(out);
-  const int nblk = (int)std::min<long long>(4096, (npx + 1023) / 1024);
-  hipStream_t st = as_stream(stream);
-  if (is_int64)
-    MSL_LAUNCH((k_colorize<long long>), dim3(nblk), dim3(256), 0, st, (const long long*)cls, npx, palette, c,
-               out, vec);
-  else
-    MSL_LAUNCH((k_colorize<int32_t>), dim3(nblk), dim3(256), 0, st, (const int32_t*)cls, npx, palette, c, out,
-               vec);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

@@ -1123,6 +1123,21 @@ def logits_argmax_up(low, out_hw):
 
 
 # --------------------------------------------------------------------------- evaluation
+def _check_label(name, label, confusion, c, ho, wo):
+    """The label / confusion pair of every predict_* wrapper: both or neither; returns the contiguous label."""
+    if (label is None) != (confusion is None):
+        raise hip.MSLError(f"{name}: label and confusion go together")
+    if label is None:
+        return None
+    label = label.contiguous()
+    if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
+        raise hip.MSLError(f"{name}: label must be a CUDA int64 tensor with {ho * wo} elements")
+    if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
+            not confusion.is_contiguous()):
+        raise hip.MSLError(f"{name}: confusion must be a contiguous CUDA int64 tensor with {c * c} elements")
+    return label
+
+
 def predict_up(low, out_hw, low_flip=None, label=None, confusion=None, want_argmax=False):
     """The evaluator's per-pixel class (tools/evaluate.py:114-141) from the low-resolution logits
     `low` (1,C,hi,wi), fused with the confusion matrix (msl_predict_up): np.argmax of the upsampled
@@ -1136,16 +1151,8 @@ def predict_up(low, out_hw, low_flip=None, label=None, confusion=None, want_argm
         low_flip = _check_act(low_flip.detach(), "predict_up")
         if low_flip.shape != low.shape:
             raise hip.MSLError("predict_up: low_flip must have low's shape")
-    if (label is None) != (confusion is None):
-        raise hip.MSLError("predict_up: label and confusion go together")
-    if label is not None:
-        label = label.contiguous()
-        if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
-            raise hip.MSLError(f"predict_up: label must be a CUDA int64 tensor with {ho * wo} elements")
-        if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
-                not confusion.is_contiguous()):
-            raise hip.MSLError(f"predict_up: confusion must be a contiguous CUDA int64 tensor with {c * c} elements")
-    elif not want_argmax:
+    label = _check_label("predict_up", label, confusion, c, ho, wo)
+    if label is None and not want_argmax:
         raise hip.MSLError("predict_up: nothing to compute (no label / confusion and want_argmax=False)")
     arg = torch.empty(ho * wo, dtype=torch.int32, device=low.device) if want_argmax else None
     hip.check(hip.load().msl_predict_up(low.data_ptr(), hip.ptr(low_flip), c, hi, wi, ho, wo, hip.ptr(label),
@@ -1166,16 +1173,8 @@ def predict_rectify(low, crop0, crop1, out_hw, segy0, label=None, confusion=None
         if t.shape != low.shape:
             raise hip.MSLError("predict_rectify: the crops' logits must have low's shape")
         crops.append(t)
-    if (label is None) != (confusion is None):
-        raise hip.MSLError("predict_rectify: label and confusion go together")
-    if label is not None:
-        label = label.contiguous()
-        if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
-            raise hip.MSLError(f"predict_rectify: label must be a CUDA int64 tensor with {ho * wo} elements")
-        if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
-                not confusion.is_contiguous()):
-            raise hip.MSLError(f"predict_rectify: confusion must be a contiguous CUDA int64 tensor with {c * c} elements")
-    elif not want_argmax:
+    label = _check_label("predict_rectify", label, confusion, c, ho, wo)
+    if label is None and not want_argmax:
         raise hip.MSLError("predict_rectify: nothing to compute (no label / confusion and want_argmax=False)")
     arg = torch.empty(ho * wo, dtype=torch.int32, device=low.device) if want_argmax else None
     hip.check(hip.load().msl_predict_rectify(low.data_ptr(), crops[0].data_ptr(), crops[1].data_ptr(), c, hi, wi, ho, wo,
@@ -1211,6 +1210,21 @@ def image_buffers(out_hw, want, device):
     return {k: torch.empty((ho, wo) + IMAGE_MAPS[k], dtype=torch.uint8, device=device) for k in want}
 
 
+def _image_outputs(name, out, want, ho, wo, device, label):
+    """The checked output maps of an image wrapper: `out`, or fresh buffers for `want`; with neither a map nor a
+    label there is nothing to compute."""
+    if out is None:
+        out = image_buffers((ho, wo), want, device)
+    for k, t in out.items():
+        if (k not in IMAGE_MAPS or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or
+                tuple(t.shape) != (ho, wo) + IMAGE_MAPS[k]):
+            raise hip.MSLError(f"{name}: output {k!r} must be a contiguous CUDA uint8 tensor of shape "
+                               f"{(ho, wo) + IMAGE_MAPS.get(k, ())}")
+    if not out and label is None:
+        raise hip.MSLError(f"{name}: nothing to compute (no map and no label / confusion)")
+    return out
+
+
 def predict_images(low, out_hw, low_flip=None, label=None, confusion=None, want=("color",), thr=0.95, out=None):
     """predict_up's decision as uint8 images, in the same single launch (msl_predict_images).  `want` names
     the maps (IMAGE_MAPS): "class" (ho,wo) the class index, "ids" (ho,wo) its Cityscapes labelId, "color"
@@ -1224,25 +1238,8 @@ def predict_images(low, out_hw, low_flip=None, label=None, confusion=None, want=
         low_flip = _check_act(low_flip.detach(), "predict_images")
         if low_flip.shape != low.shape:
             raise hip.MSLError("predict_images: low_flip must have low's shape")
-    if (label is None) != (confusion is None):
-        raise hip.MSLError("predict_images: label and confusion go together")
-    if label is not None:
-        label = label.contiguous()
-        if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
-            raise hip.MSLError(f"predict_images: label must be a CUDA int64 tensor with {ho * wo} elements")
-        if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
-                not confusion.is_contiguous()):
-            raise hip.MSLError(f"predict_images: confusion must be a contiguous CUDA int64 tensor with {c * c} "
-                               "elements")
-    if out is None:
-        out = image_buffers((ho, wo), want, low.device)
-    for k, t in out.items():
-        if (k not in IMAGE_MAPS or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or
-                tuple(t.shape) != (ho, wo) + IMAGE_MAPS[k]):
-            raise hip.MSLError(f"predict_images: output {k!r} must be a contiguous CUDA uint8 tensor of shape "
-                               f"{(ho, wo) + IMAGE_MAPS.get(k, ())}")
-    if not out and label is None:
-        raise hip.MSLError("predict_images: nothing to compute (no map and no label / confusion)")
+    label = _check_label("predict_images", label, confusion, c, ho, wo)
+    out = _image_outputs("predict_images", out, want, ho, wo, low.device, label)
     id_lut, pal, shade = image_tables(c, low.device)
     hip.check(hip.load().msl_predict_images(
         low.data_ptr(), hip.ptr(low_flip), c, hi, wi, ho, wo, hip.ptr(label), hip.ptr(confusion), float(thr),
@@ -1272,20 +1269,6 @@ def _tta_table(entries, name):
     return table, lows, c
 
 
-def _tta_label(name, label, confusion, c, ho, wo):
-    if (label is None) != (confusion is None):
-        raise hip.MSLError(f"{name}: label and confusion go together")
-    if label is None:
-        return None
-    label = label.contiguous()
-    if not label.is_cuda or label.dtype != torch.int64 or label.numel() != ho * wo:
-        raise hip.MSLError(f"{name}: label must be a CUDA int64 tensor with {ho * wo} elements")
-    if (not confusion.is_cuda or confusion.dtype != torch.int64 or confusion.numel() != c * c or
-            not confusion.is_contiguous()):
-        raise hip.MSLError(f"{name}: confusion must be a contiguous CUDA int64 tensor with {c * c} elements")
-    return label
-
-
 def predict_tta(entries, out_hw, label=None, confusion=None, want_argmax=False):
     """Multi-scale / mirror test-time augmentation in one launch (msl_predict_tta).  `entries`: (low, mirror)
     pairs, low (1,C,hi,wi) the low-resolution logits of the image at some input scale, mirror 1 when they are
@@ -1294,7 +1277,7 @@ def predict_tta(entries, out_hw, label=None, confusion=None, want_argmax=False):
     is predict_up's --flip class bit for bit.  label / confusion / want_argmax as predict_up."""
     table, lows, c = _tta_table(entries, "predict_tta")
     ho, wo = int(out_hw[0]), int(out_hw[1])
-    label = _tta_label("predict_tta", label, confusion, c, ho, wo)
+    label = _check_label("predict_tta", label, confusion, c, ho, wo)
     if label is None and not want_argmax:
         raise hip.MSLError("predict_tta: nothing to compute (no label / confusion and want_argmax=False)")
     arg = torch.empty(ho * wo, dtype=torch.int32, device=lows[0].device) if want_argmax else None
@@ -1309,16 +1292,8 @@ def predict_tta_images(entries, out_hw, label=None, confusion=None, want=("color
     the class divided by the number of entries.  `want`, `thr`, `out` and the result as predict_images."""
     table, lows, c = _tta_table(entries, "predict_tta_images")
     ho, wo = int(out_hw[0]), int(out_hw[1])
-    label = _tta_label("predict_tta_images", label, confusion, c, ho, wo)
-    if out is None:
-        out = image_buffers((ho, wo), want, lows[0].device)
-    for k, t in out.items():
-        if (k not in IMAGE_MAPS or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or
-                tuple(t.shape) != (ho, wo) + IMAGE_MAPS[k]):
-            raise hip.MSLError(f"predict_tta_images: output {k!r} must be a contiguous CUDA uint8 tensor of shape "
-                               f"{(ho, wo) + IMAGE_MAPS.get(k, ())}")
-    if not out and label is None:
-        raise hip.MSLError("predict_tta_images: nothing to compute (no map and no label / confusion)")
+    label = _check_label("predict_tta_images", label, confusion, c, ho, wo)
+    out = _image_outputs("predict_tta_images", out, want, ho, wo, lows[0].device, label)
     id_lut, pal, shade = image_tables(c, lows[0].device)
     hip.check(hip.load().msl_predict_tta_images(
         table, len(lows), c, ho, wo, hip.ptr(label), hip.ptr(confusion), float(thr), id_lut.data_ptr(),

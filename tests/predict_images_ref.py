@@ -22,7 +22,7 @@ import evaluate_ref as ev
 SPLITS = (0.9, 0.8, 0.7, 0.5)
 THR = 0.95
 NEAR_EDGE = 1e-5
-GRID_CAP = 1024  # kPredictBlocks of csrc/loss.hip: blocks of 256 threads, four pixels per thread
+GRID_CAP = 1024  # kPredictBlocks of csrc/predict.hip: blocks of 256 threads, four pixels per thread
 # (C, hi, wi, ho, wo): wo % 4 != 0 in one block; the dword path; odd wo (the mirror column); several blocks; and
 # more pixels than one pass of the capped grid covers (1028 * 1032 > 1024 * 256 * 4)
 SHAPES = [(13, 3, 3, 7, 9), (19, 5, 7, 12, 16), (16, 5, 9, 40, 71), (19, 9, 17, 33, 65), (19, 33, 65, 1028, 1032)]

@@ -151,7 +151,7 @@ def test_new_entry_points_are_declared_and_exported():
     for fn in ("style_input_window", "style_output_resampled", "label_resize_nearest", "predict_rectify"):
         assert callable(getattr(ops, fn))
     # the rectification kernels neither spill nor use scratch (the build's resource report)
-    path = os.path.join(ROOT, "maxsquareloss_amd", "_lib", "obj", "loss.o.remarks")
+    path = os.path.join(ROOT, "maxsquareloss_amd", "_lib", "obj", "predict.o.remarks")
     if os.path.exists(path):
         text = open(path).read()
         blocks = re.findall(r"Function Name: (\S*k_predict_rectify\S*)(.*?)(?=Function Name:|\Z)", text, flags=re.S)

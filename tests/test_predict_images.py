@@ -40,9 +40,9 @@ def test_entry_points_declared_bound_and_exported(name, nargs):
 
 
 def test_image_kernels_use_no_scratch():
-    """The compiler's resource report of the last build (Makefile: loss.o.remarks): no instantiation of the
+    """The compiler's resource report of the last build (Makefile: predict.o.remarks): no instantiation of the
     prediction kernels spills or uses scratch, and the shared per-pixel decision left k_predict_up without any."""
-    path = os.path.join(ROOT, "maxsquareloss_amd", "_lib", "obj", "loss.o.remarks")
+    path = os.path.join(ROOT, "maxsquareloss_amd", "_lib", "obj", "predict.o.remarks")
     if not os.path.exists(path):
         pytest.skip("no resource report: build the library first (__graft_entry__.build())")
     kern, info = None, {}

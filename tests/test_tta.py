@@ -105,13 +105,14 @@ def test_resize_bilinear_refuses_before_any_launch():
 
 
 def test_fusion_kernels_use_no_scratch():
-    """The compiler's resource report of the last build (Makefile: loss.o.remarks): the by-value entry table,
-    indexed with the loop variable, puts nothing in scratch and nothing spills, in any instantiation."""
-    path = os.path.join(ROOT, "maxsquareloss_amd", "_lib", "obj", "loss.o.remarks")
-    if not os.path.exists(path):
+    """The compiler's resource report of the last build (Makefile: predict.o.remarks, and loss.o.remarks for
+    k_resize_four): the by-value entry table, indexed with the loop variable, puts nothing in scratch and nothing
+    spills, in any instantiation."""
+    paths = [os.path.join(ROOT, "maxsquareloss_amd", "_lib", "obj", o + ".remarks") for o in ("predict.o", "loss.o")]
+    if not all(os.path.exists(p) for p in paths):
         pytest.skip("no resource report: build the library first (__graft_entry__.build())")
     kern, info = None, {}
-    for line in open(path):
+    for line in (line for p in paths for line in open(p)):
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             kern = m.group(1)
