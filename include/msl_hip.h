@@ -776,6 +776,46 @@ int msl_predict_tta_images(const msl_tta_entry* entries, int n, int c, int ho, i
 int msl_colorize(const void* cls, int is_int64, long long npx, const uint8_t* palette, int c, uint8_t* out,
                  msl_stream_t stream);
 
+/* Per-image analysis (the reference's tools/analysis.py), decided on the device.
+ *
+ * msl_image_metrics: one image's scores from image_cm, the uint64 [c*c] matrix its prediction launch just
+ * filled (confusion[gt * c + class]), by the definitions of utils/eval.py:Eval.  Row sums r, column sums
+ * s, the diagonal d and the total are exact uint64 sums converted to fp64 once; per class acc = d / r and
+ * iou = d / (r + s - d), 0/0 = NaN as in numpy (each bit-equal to numpy's); PA = trace / total, 0 when
+ * total is 0; MPA and MIoU the nan-means, summed by one thread in class order, NaN when every class is;
+ * FWIoU = sum of r * iou over the non-NaN classes / total.  For c == 16 also the three 13-class values
+ * over synthia_set_16_to_13 (FWIoU_13 divides by the same total).  Row state[0] % capacity of rows
+ * (fp64 [capacity][9 + c]) receives
+ *   [PA, MPA, MIoU, FWIoU, MPA_13, MIoU_13, FWIoU_13, pixels, selected, iou[0..c-1]]
+ * (the _13 fields NaN unless c == 16; pixels = total), selected = (m < threshold) ? 1 : 0 with m the MIoU
+ * utils/validate.py:val_info returns (the 13-class one for 16 classes): strict, a NaN is not selected.  Then
+ * total_cm += image_cm, image_cm = 0, and state (three device ints {cursor, selected, slot}) becomes
+ * {cursor + 1, selected, cursor % capacity}.  One 256-thread block, nothing read by the host.
+ * MSL_ERR_ARG before any launch: a NULL pointer, c outside [1, 32], capacity < 1. */
+int msl_image_metrics(unsigned long long* image_cm, unsigned long long* total_cm, int c, double threshold,
+                      double* rows, int capacity, int* state, msl_stream_t stream);
+
+/* msl_analysis_maps: the maps of an image msl_image_metrics selected, all uint8 [h*w*3] HWC RGB, all
+ * nullable, at least one required:
+ *   label_out  palette[label] for a label in [0, c), else black (decode_labels);
+ *   pred_out   palette[cls], cls the uint8 [h*w] class map of msl_predict_images (class_out);
+ *   input_out  channel 2-k of clamp(rint(x[k] + mean[k]), 0, 255), round half to even, NaN -> 0, x the fp32
+ *              network input [3][h][w] (BGR - mean), mean a device fp32 [3]: utils/images.py:recover_input;
+ *   error_out  black where the label is outside [0, c), input_out >> 1 per byte where cls == label,
+ *              palette[cls] where they differ.
+ * palette is a device uint8 [c*3].  With state (msl_image_metrics') every thread first reads state[1] and
+ * returns on 0 before any other load or store - the device-side gate - and otherwise every map is written
+ * at out + state[2] * slot_stride (bytes); state == NULL always writes, at out.  A thread takes four pixels
+ * of a row: float4 loads and dword stores when w % 4 == 0, x is 16-byte and cls, the outputs and slot_stride
+ * 4-byte aligned, else scalar loads and byte stores.
+ * MSL_ERR_ARG before any launch: no output, an input NULL that a requested map reads (label: label_out,
+ * error_out; x, mean: input_out, error_out; cls: pred_out, error_out; palette: all but input_out), c outside
+ * [1, 32], h or w < 1, h * w >= 2^31, slot_stride < 0. */
+int msl_analysis_maps(const float* x, const float* mean, const long long* label, const uint8_t* cls,
+                      const uint8_t* palette, int c, int h, int w, const int* state, long long slot_stride,
+                      uint8_t* label_out, uint8_t* pred_out, uint8_t* input_out, uint8_t* error_out,
+                      msl_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Input pipeline (the loaders' last host steps, on the device after a uint8 H2D copy; byte-exact):
  *   msl_image_transform: out[c][y][x] = (float)rgb[y][xs][2 - c] - mean[c] (BGR order, mean =

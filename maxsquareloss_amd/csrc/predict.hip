@@ -429,6 +429,116 @@ __global__ void __launch_bounds__(256) k_colorize(const T* __restrict__ cls, lon
   }
 }
 
+// ---------------------------------------------------------------- the failure maps of one image
+// Per-image analysis (the reference's tools/analysis.py:208-227): the label, the prediction and the input of an
+// image whose MIoU fell below the threshold, as RGB maps, plus an error map.  Whether to write at all was
+// decided on the device by msl_image_metrics (eval.hip): with `state` every thread reads state[1] first and
+// returns on 0 before any other load or store; otherwise the maps go to slot state[2] of the ring.  The
+// four-pixels-per-thread layout of predict_images: with VEC a float4 per input plane, a dword of classes and
+// three dwords per RGB map, without it every pixel loads and stores its own.
+struct MapsOut {
+  uint8_t* label;  // [H*W*3] palette[label], black outside [0, C)  (decode_labels)
+  uint8_t* pred;   // [H*W*3] palette[cls]
+  uint8_t* input;  // [H*W*3] the uint8 RGB image the network input was made from  (recover_input)
+  uint8_t* error;  // [H*W*3] black where unlabelled, the dimmed input where right, palette[cls] where wrong
+};
+
+// one byte of utils/images.py:recover_input: clamp(rint(x + mean), 0, 255), round half to even, NaN -> 0
+__device__ __forceinline__ unsigned int input_byte(float x, float m) {
+  const float v = rintf(x + m);
+  return v >= 0.f ? (unsigned int)fminf(v, 255.f) : 0u;
+}
+
+__global__ void __launch_bounds__(256) k_analysis_maps(const float* __restrict__ x, const float* __restrict__ mean,
+                                                       const long long* __restrict__ label,
+                                                       const uint8_t* __restrict__ cls,
+                                                       const uint8_t* __restrict__ palette, int C, int H, int W,
+                                                       const int* __restrict__ state, long long slot_stride,
+                                                       MapsOut o, int vec) {
+  long long off = 0;
+  if (state) {
+    if (state[1] == 0) return;  // the device-side gate: uniform over the grid
+    off = (long long)state[2] * slot_stride;
+  }
+  __shared__ unsigned int t_pal[kMaxC];
+  if ((int)threadIdx.x < C) t_pal[threadIdx.x] = palette ? rgb24(palette, threadIdx.x) : 0u;
+  __syncthreads();
+  uint8_t* const o_label = o.label ? o.label + off : nullptr;
+  uint8_t* const o_pred = o.pred ? o.pred + off : nullptr;
+  uint8_t* const o_input = o.input ? o.input + off : nullptr;
+  uint8_t* const o_error = o.error ? o.error + off : nullptr;
+  // what the requested maps read (the host checked that it is there): nothing else is loaded or looked up
+  const bool want_in = o.input || o.error, want_lab = o.label || o.error, want_cls = o.pred || o.error;
+  float m[3] = {0.f, 0.f, 0.f};
+  if (want_in) {
+    m[0] = mean[0];
+    m[1] = mean[1];
+    m[2] = mean[2];
+  }
+  const long long plane = (long long)H * W;    // < 2^31 (the host checks)
+  const int nq = (W + 3) >> 2;                 // quads per row
+  const long long nquad = (long long)H * nq;
+  for (long long qq = blockIdx.x * 256LL + threadIdx.x; qq < nquad; qq += (long long)gridDim.x * 256) {
+    const int oy = (int)(qq / nq), ox0 = (int)(qq - (long long)oy * nq) << 2;
+    const long long px0 = (long long)oy * W + ox0;
+    const int n = vec ? 4 : min(4, W - ox0);
+    float xv[3][4];
+    unsigned int cw = 0u;
+    if (vec) {  // px0 == 4 * qq
+      if (want_in) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float4 f = *reinterpret_cast<const float4*>(x + k * plane + px0);
+          xv[k][0] = f.x;
+          xv[k][1] = f.y;
+          xv[k][2] = f.z;
+          xv[k][3] = f.w;
+        }
+      }
+      if (want_cls) cw = *reinterpret_cast<const unsigned int*>(cls + px0);
+    }
+    unsigned int lc[4], pc[4], ic[4], ec[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      lc[j] = pc[j] = ic[j] = ec[j] = 0u;
+      if (j < n) {
+        const long long px = px0 + j;
+        unsigned int cb = (cw >> (8 * j)) & 255u;
+        if (!vec) {
+          if (want_cls) cb = cls[px];
+          if (want_in) {
+            xv[0][j] = x[px];
+            xv[1][j] = x[plane + px];
+            xv[2][j] = x[2 * plane + px];
+          }
+        }
+        const long long y = want_lab ? label[px] : -1;
+        const bool valid = y >= 0 && y < C;
+        lc[j] = valid ? t_pal[(int)y] : 0u;
+        if (want_cls) pc[j] = (int)cb < C ? t_pal[cb] : 0u;
+        if (want_in)  // RGB = channels 2, 1, 0 of the BGR input
+          ic[j] = input_byte(xv[2][j], m[2]) | (input_byte(xv[1][j], m[1]) << 8) | (input_byte(xv[0][j], m[0]) << 16);
+        if (o.error) ec[j] = !valid ? 0u : (long long)cb == y ? (ic[j] >> 1) & 0x7f7f7fu : pc[j];
+      }
+    }
+    if (vec) {
+      if (o_label) store_rgb4(o_label, qq, lc[0], lc[1], lc[2], lc[3]);
+      if (o_pred) store_rgb4(o_pred, qq, pc[0], pc[1], pc[2], pc[3]);
+      if (o_input) store_rgb4(o_input, qq, ic[0], ic[1], ic[2], ic[3]);
+      if (o_error) store_rgb4(o_error, qq, ec[0], ec[1], ec[2], ec[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < n) {
+          if (o_label) store_rgb1(o_label, px0 + j, lc[j]);
+          if (o_pred) store_rgb1(o_pred, px0 + j, pc[j]);
+          if (o_input) store_rgb1(o_input, px0 + j, ic[j]);
+          if (o_error) store_rgb1(o_error, px0 + j, ec[j]);
+        }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- host helpers
 // What a call computes into: label and confusion go together, and there is a matrix or an output.
 static bool sinks_ok(const long long* label, const unsigned long long* confusion, bool any_out) {
@@ -579,6 +689,27 @@ int msl_colorize(const void* cls, int is_int64, long long npx, const uint8_t* pa
   else
     MSL_LAUNCH((k_colorize<int32_t>), dim3(nblk), dim3(256), 0, st, (const int32_t*)cls, npx, palette, c, out,
                vec);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_analysis_maps(const float* x, const float* mean, const long long* label, const uint8_t* cls,
+                      const uint8_t* palette, int c, int h, int w, const int* state, long long slot_stride,
+                      uint8_t* label_out, uint8_t* pred_out, uint8_t* input_out, uint8_t* error_out,
+                      msl_stream_t stream) {
+  const MapsOut o = {label_out, pred_out, input_out, error_out};
+  if (!(label_out || pred_out || input_out || error_out) || c < 1 || c > kMaxC || h < 1 || w < 1 ||
+      (long long)h * w >= (1LL << 31) || slot_stride < 0)
+    return MSL_ERR_ARG;
+  // what each map reads
+  if (((label_out || error_out) && !label) || ((input_out || error_out) && (!x || !mean)) ||
+      ((pred_out || error_out) && !cls) || ((label_out || pred_out || error_out) && !palette))
+    return MSL_ERR_ARG;
+  const int vec = w % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && dword_aligned(cls) &&
+                  dword_aligned(label_out) && dword_aligned(pred_out) && dword_aligned(input_out) &&
+                  dword_aligned(error_out) && slot_stride % 4 == 0;
+  MSL_LAUNCH(k_analysis_maps, dim3(image_blocks(h, w)), dim3(256), 0, as_stream(stream), x, mean, label, cls,
+             palette, c, h, w, state, slot_stride, o, vec);
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

@@ -1319,6 +1319,96 @@ def colorize(mask, palette):
     return out
 
 
+# --------------------------------------------------------------------------- per-image analysis
+METRICS_HEAD = ("PA", "MPA", "MIoU", "FWIoU", "MPA_13", "MIoU_13", "FWIoU_13", "pixels", "selected")
+ANALYSIS_MAPS = ("label", "pred", "input", "error")  # msl_analysis_maps' outputs, in its argument order
+_MEAN_TABLES = {}  # device -> IMG_MEAN as fp32 [3] on the device
+
+
+def metrics_buffers(num_classes, capacity, device):
+    """(rows fp64 [capacity, 9 + C], state int32 [3] = {cursor, selected, slot}) of image_metrics, zeroed."""
+    return (torch.zeros((int(capacity), len(METRICS_HEAD) + int(num_classes)), dtype=torch.float64, device=device),
+            torch.zeros(3, dtype=torch.int32, device=device))
+
+
+def image_metrics(image_cm, total_cm, threshold, rows, state):
+    """One image's scores on the device (msl_image_metrics): from `image_cm`, the int64 [C*C] matrix the
+    image's prediction launch just filled, row state[0] % capacity of `rows` (metrics_buffers) becomes
+    [PA, MPA, MIoU, FWIoU, MPA_13, MIoU_13, FWIoU_13, pixels, selected, iou[0..C-1]] by utils/eval.py:Eval's
+    definitions, selected = val_info's MIoU < threshold (strict; NaN is not selected); then total_cm +=
+    image_cm, image_cm = 0 and `state` = {cursor + 1, selected, slot}.  Nothing syncs."""
+    cc = image_cm.numel()
+    c = int(round(cc ** 0.5))
+    for name, t in (("image_cm", image_cm), ("total_cm", total_cm)):
+        if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != cc or c * c != cc:
+            raise hip.MSLError(f"image_metrics: {name} must be a contiguous CUDA int64 tensor with C*C elements")
+    if (not rows.is_cuda or rows.dtype != torch.float64 or not rows.is_contiguous() or rows.dim() != 2 or
+            rows.size(0) < 1 or rows.size(1) != len(METRICS_HEAD) + c):
+        raise hip.MSLError(f"image_metrics: rows must be a contiguous CUDA float64 [capacity, {len(METRICS_HEAD) + c}]")
+    if not state.is_cuda or state.dtype != torch.int32 or not state.is_contiguous() or state.numel() != 3:
+        raise hip.MSLError("image_metrics: state must be a contiguous CUDA int32 tensor with 3 elements")
+    hip.check(hip.load().msl_image_metrics(image_cm.data_ptr(), total_cm.data_ptr(), c, float(threshold),
+                                           rows.data_ptr(), rows.size(0), state.data_ptr(), hip.stream_ptr()),
+              "msl_image_metrics")
+
+
+def analysis_buffers(hw, want, slots, device):
+    """Empty uint8 [slots, h, w, 3] rings of analysis_maps for the maps in `want`."""
+    bad = [k for k in want if k not in ANALYSIS_MAPS]
+    if bad:
+        raise hip.MSLError(f"analysis_maps: unknown maps {bad}; choose from {list(ANALYSIS_MAPS)}")
+    return {k: torch.empty((int(slots), int(hw[0]), int(hw[1]), 3), dtype=torch.uint8, device=device) for k in want}
+
+
+def analysis_maps(x, label, cls, num_classes, want=("label", "pred", "input"), state=None, out=None, palette=None):
+    """The failure maps of one image (msl_analysis_maps), uint8 (h, w, 3) RGB each: "label" the label's
+    colours (black outside [0, C)), "pred" those of `cls` - the uint8 (h, w) class map of predict_images -,
+    "input" the image recovered from the network input `x` (1,3,h,w) (utils/images.py:recover_input's bytes),
+    "error" black where unlabelled, the dimmed input where cls == label, the predicted colour where not.
+    `state`: image_metrics' - the launch returns at once unless state[1], and writes slot state[2] of `out`.
+    `out`: rings from analysis_buffers (then `want` is its keys; without `state` slot 0 is written); else fresh
+    one-slot buffers.  `palette`: a CUDA uint8 [C, 3] instead of the class count's own.  Returns the dict."""
+    c = int(num_classes)
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.size(0) != 1 or x.size(1) != 3:
+        raise hip.MSLError("analysis_maps: x must be a CUDA fp32 (1, 3, h, w) network input")
+    x = x.contiguous()
+    h, w = int(x.shape[2]), int(x.shape[3])
+    if out is None:
+        out = analysis_buffers((h, w), want, 1, x.device)
+    if not out:
+        raise hip.MSLError("analysis_maps: nothing to compute (no map)")
+    slots = {int(t.shape[0]) if t.dim() == 4 else -1 for t in out.values()}
+    for k, t in out.items():
+        if (k not in ANALYSIS_MAPS or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or
+                t.dim() != 4 or tuple(t.shape[1:]) != (h, w, 3)):
+            raise hip.MSLError(f"analysis_maps: output {k!r} must be a contiguous CUDA uint8 [slots, {h}, {w}, 3]")
+    if len(slots) != 1:
+        raise hip.MSLError("analysis_maps: the rings must have the same number of slots")
+    if label is not None:
+        label = label.contiguous()
+        if not label.is_cuda or label.dtype != torch.int64 or label.numel() != h * w:
+            raise hip.MSLError(f"analysis_maps: label must be a CUDA int64 tensor with {h * w} elements")
+    if cls is not None and (not cls.is_cuda or cls.dtype != torch.uint8 or not cls.is_contiguous() or
+                            cls.numel() != h * w):
+        raise hip.MSLError(f"analysis_maps: cls must be a contiguous CUDA uint8 tensor with {h * w} elements")
+    if state is not None and (not state.is_cuda or state.dtype != torch.int32 or not state.is_contiguous() or
+                              state.numel() != 3):
+        raise hip.MSLError("analysis_maps: state must be a contiguous CUDA int32 tensor with 3 elements")
+    if palette is None:
+        palette = image_tables(c, x.device)[1]
+    elif (not palette.is_cuda or palette.dtype != torch.uint8 or not palette.is_contiguous() or
+          palette.numel() != 3 * c):
+        raise hip.MSLError(f"analysis_maps: palette must be a contiguous CUDA uint8 [{c}, 3]")
+    if x.device not in _MEAN_TABLES:
+        from .utils.synthetic import IMG_MEAN
+        _MEAN_TABLES[x.device] = torch.tensor([float(v) for v in IMG_MEAN], dtype=torch.float32, device=x.device)
+    hip.check(hip.load().msl_analysis_maps(
+        x.data_ptr(), _MEAN_TABLES[x.device].data_ptr(), hip.ptr(label), hip.ptr(cls), palette.data_ptr(), c, h, w,
+        hip.ptr(state), h * w * 3, *(hip.ptr(out.get(k)) for k in ANALYSIS_MAPS), hip.stream_ptr()),
+        "msl_analysis_maps")
+    return out
+
+
 # --------------------------------------------------------------------------- soft cross-entropy, explicit target
 class _SoftCE(Function):
     """softCrossEntropy (ratio None) / IWsoftCrossEntropy on (1,C,H,W) logits and an explicit target."""

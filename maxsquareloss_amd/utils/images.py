@@ -28,6 +28,7 @@ SAVE_KINDS = ("color", "trainids", "labelids", "confidence", "pseudo", "input")
 # kind -> the map of ops.predict_images it is ("input" comes from the network input instead)
 KIND_MAP = {"color": "color", "trainids": "class", "labelids": "ids", "confidence": "confidence", "pseudo": "pseudo"}
 MAX_WRITER_THREADS = 16
+MAX_WRITER_SLOTS = 64
 SUMMARY_EVERY = 20  # the reference's image-summary cadence (evaluate.py: every 20th item and the last)
 
 
@@ -114,9 +115,11 @@ class ImageWriter:
     """save(name, {kind: uint8 map}) writes <directory>/<kind>/<name>.png for every kind given; device
     tensors are copied on the current stream.  `workers` host threads (at most 16) encode; each save uses
     the next of max(2, workers + 1) host slots and first waits for the encode that last used it.
-    save_as(relpath, map) writes one map to <directory>/<relpath> the same way (tools/stylize.py)."""
+    save_as(relpath, map) writes one map to <directory>/<relpath> the same way (tools/stylize.py).  `slots`
+    asks for more host slots than that (at most MAX_WRITER_SLOTS): a caller that hands over many maps at
+    once (utils/analysis.py's drain) is then not held up by the encoders while it does."""
 
-    def __init__(self, directory, kinds=SAVE_KINDS, workers=0):
+    def __init__(self, directory, kinds=SAVE_KINDS, workers=0, slots=None):
         try:
             from PIL import Image  # noqa: F401
         except ImportError as e:
@@ -127,7 +130,7 @@ class ImageWriter:
             os.makedirs(os.path.join(self.directory, k), exist_ok=True)
         self.workers = max(0, min(int(workers), MAX_WRITER_THREADS))
         self._pool = ThreadPoolExecutor(self.workers, thread_name_prefix="msl-png") if self.workers else None
-        self._slots = [_Slot() for _ in range(max(2, self.workers + 1))]
+        self._slots = [_Slot() for _ in range(max(2, self.workers + 1, min(int(slots or 0), MAX_WRITER_SLOTS)))]
         self._n = 0
         self.written = []
 
