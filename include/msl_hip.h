@@ -770,6 +770,42 @@ int msl_predict_tta_images(const msl_tta_entry* entries, int n, int c, int ho, i
                            const uint8_t* palette, const uint8_t* shade, uint8_t* class_out, uint8_t* ids_out,
                            uint8_t* color_out, uint8_t* conf_out, uint8_t* pseudo_out, msl_stream_t stream);
 
+/* Class-balanced pseudo-label thresholds (--threshold_mode class; CBST, BDL; not in the reference, whose
+ * train_round() opens with "# generate threshold" and assigns the constant).  Additive: ABI 3.
+ *
+ * msl_confidence_hist: per pixel of ho x wo, k = the class msl_predict_up gives from the same inputs, top =
+ * the probability behind msl_predict_images' pseudo_out, b = min(bins - 1, (int)(top * (float)bins)) in fp32,
+ * and hist[k * bins + b] += 1 (uint64 [c*bins] on the device).  A NaN pixel is not counted.  hist
+ * accumulates across calls: the caller zeroes it once per pass.  Integer atomics: exact, the same bytes on
+ * every run.  msl_confidence_hist_tta is the same over an entry table (k, top as msl_predict_tta_images).
+ * MSL_ERR_ARG before any launch: NULL logits or hist, c outside [1, 32], bins not a power of two in
+ * [16, 1024], c * bins > 16384 (the per-block LDS tile), msl_predict_up's geometry errors or
+ * msl_predict_tta's table errors. */
+int msl_confidence_hist(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                        int bins, unsigned long long* hist, msl_stream_t stream);
+int msl_confidence_hist_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, int bins,
+                            unsigned long long* hist, msl_stream_t stream);
+
+/* One threshold per class from such a histogram, one block, nothing read by the host.  Per class k: N = the
+ * row's sum, need = (uint64)ceil(portion * (double)N), b* = the largest bin index whose suffix sum
+ * sum_{b >= b*} hist[k][b] reaches need (need == 0: b* = bins), q = (float)b* / (float)bins and
+ * thr[k] = min(thr_max, q); N == 0 gives thr_max.  So every class keeps at least `portion` of its pixels and
+ * no threshold exceeds thr_max (portion 0.5, thr_max 0.9: BDL's rule).  kept (uint64 [c], nullable) receives
+ * sum_{b >= floor(thr[k] * bins)} hist[k][b].  thr is a device fp32 [c].
+ * MSL_ERR_ARG: a NULL hist or thr, portion outside [0, 1], thr_max outside (0, 1], the size errors above. */
+int msl_class_thresholds(const unsigned long long* hist, int c, int bins, double portion, float thr_max,
+                         float* thr, unsigned long long* kept, msl_stream_t stream);
+
+/* The pseudo-label under those thresholds, k and top as above: label[px] (int64 [ho*wo], nullable) =
+ * top > thr[k] ? k : -1 (strict; a NaN pixel is -1), pseudo[px] (uint8 [ho*wo], nullable) the same with 255
+ * for -1; at least one of them.  thr is read from device memory by the kernel, so a captured launch picks up
+ * new values.  Four pixels of a row per thread; pseudo is stored as dwords when wo % 4 == 0 and it is
+ * 4-byte aligned.  MSL_ERR_ARG: NULL logits or thr, no output, the geometry / table errors above. */
+int msl_pseudo_classwise(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                         const float* thr, long long* label, uint8_t* pseudo, msl_stream_t stream);
+int msl_pseudo_classwise_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, const float* thr,
+                             long long* label, uint8_t* pseudo, msl_stream_t stream);
+
 /* decode_labels (datasets/cityscapes_Dataset.py:352-377) on the device: out[px] = palette[cls[px]] for
  * the npx elements of a class map (int64 when is_int64, else int32), out uint8 [npx*3] HWC RGB, palette a
  * device uint8 [c*3], c <= 256; values outside [0, c), -1 included, are black. */

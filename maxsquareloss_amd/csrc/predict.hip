@@ -5,12 +5,16 @@
 //   msl_predict_rectify                          tools/train_source.py:353-381 (Trainer.rectification)
 //   msl_predict_tta / msl_predict_tta_images     multi-scale / mirror fusion over an entry table
 //   msl_colorize                                 datasets/cityscapes_Dataset.py:352-377 (decode_labels)
+//   msl_confidence_hist / msl_class_thresholds / msl_pseudo_classwise
+//                                                class-balanced pseudo-label thresholds (--threshold_mode class)
 //
-// Five kernels, three questions.  Where the class of a pixel comes from is a *source* (UpSource,
-// RectifySource, TtaSource): it yields the class of (oy, ox) and, for the image maps only, the winning
-// probability.  What is done with the classes is a *body*: predict_classes (a class per thread-pixel, the
-// optional int32 map) or predict_images (four pixels of a row per thread, the uint8 maps).  Both count the
-// (label, class) pairs in the one confusion tile.  A __global__ kernel is a source handed to a body.
+// Where the class of a pixel comes from is a *source* (UpSource, RectifySource, TtaSource): it yields the
+// class of (oy, ox) and, for the image maps and the confidence bodies, the winning probability.  What is
+// done with the classes is a *body*: predict_classes (a class per thread-pixel, the optional int32 map) or
+// predict_images (four pixels of a row per thread, the uint8 maps); both count the (label, class) pairs in
+// the one confusion tile.  predict_confidence counts (class, confidence bin) pairs instead of writing, and
+// predict_classwise writes the pseudo-label under a threshold per class.  A __global__ kernel is a source
+// handed to a body.
 #include "loss_common.h"  // the pieces shared with loss.hip; no FMA contraction in this file either
 
 namespace msl {
@@ -352,7 +356,192 @@ __device__ __forceinline__ void predict_images(const Source src, int C, int Ho, 
   if (cm) tile_flush(h, cc, cm);
 }
 
+// ---------------------------------------------------------------- body: the confidence histogram
+// One add of a wave's (class, bin) keys into the block's LDS tile; key < 0 adds nothing.  On a real target
+// image most pixels of a wave are road or sky in the top bin: 64 lanes on one LDS word serialise.  So the
+// wave first merges: twice, the lowest pending lane's key is broadcast, the lanes that hold it are counted
+// with a ballot and that lane adds the count once.  What is still pending after the two rounds - the
+// spread-out rest - adds 1 per lane.  Every lane of the wave calls this, converged.
+constexpr int kMergeRounds = 2;
+__device__ __forceinline__ void tile_add_merged(unsigned int* h, int key) {
+  const int lane = threadIdx.x & 63;
+  bool pending = key >= 0;
+#pragma unroll
+  for (int r = 0; r < kMergeRounds; ++r) {
+    const unsigned long long act = __ballot(pending);
+    if (act == 0ull) break;  // wave-uniform
+    const int lead = __ffsll((long long)act) - 1;
+    const int k0 = __shfl(key, lead, 64);
+    const bool hit = pending && key == k0;
+    const unsigned long long m = __ballot(hit);
+    if (lane == lead) atomicAdd(&h[k0], (unsigned int)__popcll(m));
+    pending = pending && !hit;
+  }
+  if (pending) atomicAdd(&h[key], 1u);
+}
+
+// hist[class][bin of the source's top()] += 1 over the pixels of Ho x Wo, one pixel per thread and trip
+// (neighbouring lanes hold neighbouring pixels: what the merge above feeds on).  The tile h[C * bins] is
+// the launch's dynamic LDS; a NaN pixel (top != top) is not counted.  The trip count is the wave's, so the
+// merge's ballots see every lane.
+template <class Source>
+__device__ __forceinline__ void predict_confidence(const Source src, int C, int Ho, int Wo, int bins,
+                                                   unsigned long long* __restrict__ hist) {
+  extern __shared__ unsigned int h_conf[];
+  const int cells = C * bins;
+  tile_zero(h_conf, cells);
+  __syncthreads();
+  const long long npx = (long long)Ho * Wo;  // < 2^31 (geo_ok)
+  const long long stride = (long long)gridDim.x * 256;
+  const long long wave0 = blockIdx.x * 256LL + (threadIdx.x & ~63);  // the wave's first pixel of trip 0
+  const float fb = (float)bins;
+  for (long long base = wave0; base < npx; base += stride) {
+    const long long pp = base + (threadIdx.x & 63);
+    int key = -1;
+    if (pp < npx) {
+      const int px = (int)pp;
+      const int oy = px / Wo, ox = px - oy * Wo;
+      float v[Source::kCM], p[Source::kCM];
+      const int best = src.classify(oy, ox, v, p);
+      const float top = src.top(v, p);
+      if (!(top != top)) {
+        const int b = max(0, min(bins - 1, (int)(top * fb)));
+        key = best * bins + b;
+      }
+    }
+    tile_add_merged(h_conf, key);
+  }
+  tile_flush(h_conf, cells, hist);
+}
+
+// ---------------------------------------------------------------- body: per-class pseudo-labels
+// predict_images' pseudo map with a threshold per class, read from device memory (a captured launch
+// picks up new values): label[px] = top > thr[class] ? class : -1 as int64, pseudo[px] the same with 255
+// for -1.  The quad layout and alignment rule of predict_images for the byte map; the thresholds sit in LDS.
+template <class Source>
+__device__ __forceinline__ void predict_classwise(const Source src, int C, int Ho, int Wo,
+                                                  const float* __restrict__ thr, long long* __restrict__ label,
+                                                  uint8_t* __restrict__ pseudo, int vec) {
+  __shared__ float t_thr[kMaxC];
+  if ((int)threadIdx.x < C) t_thr[threadIdx.x] = thr[threadIdx.x];
+  __syncthreads();
+  const int nq = (Wo + 3) >> 2;                // quads per row
+  const long long nquad = (long long)Ho * nq;  // < 2^31 (geo_ok)
+  for (long long qq = blockIdx.x * 256LL + threadIdx.x; qq < nquad; qq += (long long)gridDim.x * 256) {
+    const int q = (int)qq;
+    const int oy = q / nq, ox0 = (q - oy * nq) << 2;
+    const int row = oy * Wo;
+    unsigned int w_ps = 0u;
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int ox = ox0 + j;
+      if (ox >= Wo) break;  // never with vec
+      float v[Source::kCM], p[Source::kCM];
+      const int best = src.classify(src.quad_row(oy), ox, v, p);
+      const float top = src.top(v, p);
+      const bool keep = top > t_thr[best];  // strict; false for a NaN
+      const int px = row + ox;
+      if (label) label[px] = keep ? (long long)best : -1LL;
+      const unsigned int ps = keep ? (unsigned int)best : 255u;
+      if (vec)
+        w_ps |= ps << (8 * j);
+      else if (pseudo)
+        pseudo[px] = (uint8_t)ps;
+    }
+    if (vec && pseudo) reinterpret_cast<unsigned int*>(pseudo)[q] = w_ps;  // row + ox0 == 4 * q
+  }
+}
+
+// ---------------------------------------------------------------- class-balanced thresholds
+// Suffix sums over the 64 lanes of a wave: lane l receives the sum of x over lanes >= l.
+__device__ __forceinline__ unsigned long long wave_suffix_sum(unsigned long long x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long t = __shfl_down(x, o, 64);
+    if (lane + o < 64) x += t;
+  }
+  return x;
+}
+
+// One threshold per class from its own confidence histogram (CBST / BDL): the largest bin edge q = b* / bins
+// that still keeps `portion` of the class's pixels at or above it, capped at thr_max.  One block; a wave per
+// class, lane l holding the bins [l * per, (l + 1) * per).  All integer sums: exact.
+__global__ void __launch_bounds__(256) k_class_thresholds(const unsigned long long* __restrict__ hist, int C, int bins,
+                                                          double portion, float thr_max, float* __restrict__ thr,
+                                                          unsigned long long* __restrict__ kept) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int per = bins >> 6 > 0 ? bins >> 6 : 1;  // bins is a power of two >= 16
+  const int lo = lane * per, hi = min(bins, lo + per);  // lo >= bins: an idle lane (bins < 64)
+  for (int k = wave; k < C; k += 4) {
+    const unsigned long long* hk = hist + (long long)k * bins;
+    unsigned long long s = 0ull;
+    for (int b = lo; b < hi; ++b) s += hk[b];
+    const unsigned long long suf = wave_suffix_sum(s);  // bins >= lo
+    const unsigned long long n = __shfl(suf, 0, 64);
+    const unsigned long long need = (unsigned long long)ceil(portion * (double)n);
+    int bstar = bins;  // need == 0: q = 1
+    if (need > 0ull) {
+      const unsigned long long ok = __ballot(suf >= need);  // a prefix of the lanes: suf falls with the lane
+      bstar = 0;                                            // need > n (n above 2^53 only): keep everything
+      if (ok) {
+        const int owner = 63 - __clzll((long long)ok);  // the last lane whose suffix still reaches need
+        int mine = 0;
+        if (lane == owner) {
+          unsigned long long run = suf - s;  // the bins above this lane's
+          for (int b = hi - 1; b >= lo; --b) {
+            run += hk[b];
+            if (run >= need) {
+              mine = b;
+              break;
+            }
+          }
+        }
+        bstar = __shfl(mine, owner, 64);
+      }
+    }
+    const float q = (float)bstar / (float)bins;
+    const float t = n == 0ull ? thr_max : fminf(thr_max, q);
+    if (lane == 0) thr[k] = t;
+    if (kept) {
+      const int b0 = (int)(t * (float)bins);  // floor: t >= 0
+      unsigned long long ks = 0ull;
+      for (int b = max(lo, b0); b < hi; ++b) ks += hk[b];
+      ks = wave_suffix_sum(ks);
+      if (lane == 0) kept[k] = ks;
+    }
+  }
+}
+
 // ---------------------------------------------------------------- the kernels: a source and a body
+template <int FLIP, int CM>
+__global__ void __launch_bounds__(256) k_confidence_hist(const float* __restrict__ L, const float* __restrict__ Lf,
+                                                          Geo g, int bins, unsigned long long* __restrict__ hist) {
+  predict_confidence(UpSource<FLIP, CM>{L, Lf, g}, g.C, g.Ho, g.Wo, bins, hist);
+}
+
+template <int CM>
+__global__ void __launch_bounds__(256) k_confidence_hist_tta(TtaTable t, int n, int C, int Ho, int Wo, int bins,
+                                                              unsigned long long* __restrict__ hist) {
+  predict_confidence(TtaSource<CM>{t, n, C, Wo}, C, Ho, Wo, bins, hist);
+}
+
+template <int FLIP, int CM>
+__global__ void __launch_bounds__(256) k_pseudo_classwise(const float* __restrict__ L, const float* __restrict__ Lf,
+                                                           Geo g, const float* __restrict__ thr,
+                                                           long long* __restrict__ label, uint8_t* __restrict__ pseudo,
+                                                           int vec) {
+  predict_classwise(UpSource<FLIP, CM>{L, Lf, g}, g.C, g.Ho, g.Wo, thr, label, pseudo, vec);
+}
+
+template <int CM>
+__global__ void __launch_bounds__(256) k_pseudo_classwise_tta(TtaTable t, int n, int C, int Ho, int Wo,
+                                                               const float* __restrict__ thr,
+                                                               long long* __restrict__ label,
+                                                               uint8_t* __restrict__ pseudo, int vec) {
+  predict_classwise(TtaSource<CM>{t, n, C, Wo}, C, Ho, Wo, thr, label, pseudo, vec);
+}
+
 template <int FLIP, int CM>
 __global__ void __launch_bounds__(256) k_predict_up(const float* __restrict__ L, const float* __restrict__ Lf, Geo g,
                                                      const long long* __restrict__ label,
@@ -566,6 +755,16 @@ static int image_blocks(int ho, int wo) {
   return std::min(kPredictBlocks, cdiv((long long)ho * cdiv(wo, 4), 256));
 }
 
+// predict_confidence: a power-of-two bin count (b / bins is then exact in fp32) whose tile fits 64 KB of LDS
+constexpr int kHistMaxCells = 16384;
+static bool hist_ok(int c, int bins) {
+  return bins >= 16 && bins <= 1024 && (bins & (bins - 1)) == 0 && c >= 1 && c * bins <= kHistMaxCells;
+}
+// one pixel per thread and trip, two trips until the grid cap binds: the zero and flush of the tile are paid once
+// per 512 pixels.  Measured at 1024 x 512 (profiles/pseudo_thresholds_times.txt): more pixels per block merge more
+// per flush but leave compute units idle - 2048 per block takes 1.4x to 1.7x the time of 1024, 512 takes 0.8x to 1.0x
+static int hist_blocks(int ho, int wo) { return std::min(kPredictBlocks, cdiv((long long)ho * wo, 512)); }
+
 // the caller's entries -> the kernel's table; each entry's scales are make_geo's for its own size
 static bool make_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, TtaTable* t) {
   if (!entries || n < 1 || n > kTtaMax) return false;
@@ -671,6 +870,81 @@ int msl_predict_tta_images(const msl_tta_entry* entries, int n, int c, int ho, i
                  MSL_LAUNCH((k_predict_tta_images<CM>), dim3(image_blocks(ho, wo)), dim3(256), 0,
                             as_stream(stream), t, n, c, ho, wo, label, confusion, thr, id_lut, palette, shade, o,
                             vec));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_confidence_hist(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                        int bins, unsigned long long* hist, msl_stream_t stream) {
+  if (!geo_ok(c, hi, wi, ho, wo) || !logits || !hist || !hist_ok(c, bins)) return MSL_ERR_ARG;
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  const int nblk = hist_blocks(ho, wo);
+  const size_t lds = (size_t)c * bins * sizeof(unsigned int);
+  hipStream_t st = as_stream(stream);
+  if (logits_flip)
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_confidence_hist<1, CM>), dim3(nblk), dim3(256), lds, st, logits, logits_flip, g,
+                              bins, hist));
+  else
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_confidence_hist<0, CM>), dim3(nblk), dim3(256), lds, st, logits, logits_flip, g,
+                              bins, hist));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_confidence_hist_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, int bins,
+                            unsigned long long* hist, msl_stream_t stream) {
+  TtaTable t;
+  if (!geo_ok(c, 1, 1, ho, wo) || !make_tta(entries, n, c, ho, wo, &t) || !hist || !hist_ok(c, bins))
+    return MSL_ERR_ARG;
+  const size_t lds = (size_t)c * bins * sizeof(unsigned int);
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_confidence_hist_tta<CM>), dim3(hist_blocks(ho, wo)), dim3(256), lds,
+                            as_stream(stream), t, n, c, ho, wo, bins, hist));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_class_thresholds(const unsigned long long* hist, int c, int bins, double portion, float thr_max,
+                         float* thr, unsigned long long* kept, msl_stream_t stream) {
+  if (!hist || !thr || c < 1 || c > kMaxC || !hist_ok(c, bins) || !(portion >= 0.0 && portion <= 1.0) ||
+      !(thr_max > 0.f && thr_max <= 1.f))
+    return MSL_ERR_ARG;
+  MSL_LAUNCH(k_class_thresholds, dim3(1), dim3(256), 0, as_stream(stream), hist, c, bins, portion, thr_max, thr,
+             kept);
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_pseudo_classwise(const float* logits, const float* logits_flip, int c, int hi, int wi, int ho, int wo,
+                         const float* thr, long long* label, uint8_t* pseudo, msl_stream_t stream) {
+  if (!geo_ok(c, hi, wi, ho, wo) || !logits || !thr || !(label || pseudo)) return MSL_ERR_ARG;
+  const Geo g = make_geo(c, hi, wi, ho, wo);
+  const int vec = wo % 4 == 0 && dword_aligned(pseudo);
+  const int nblk = image_blocks(ho, wo);
+  hipStream_t st = as_stream(stream);
+  if (logits_flip)
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_pseudo_classwise<1, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip, g,
+                              thr, label, pseudo, vec));
+  else
+    MSL_DISPATCH_C(c, CM,
+                   MSL_LAUNCH((k_pseudo_classwise<0, CM>), dim3(nblk), dim3(256), 0, st, logits, logits_flip, g,
+                              thr, label, pseudo, vec));
+  MSL_CHECK_LAUNCH();
+  return MSL_OK;
+}
+
+int msl_pseudo_classwise_tta(const msl_tta_entry* entries, int n, int c, int ho, int wo, const float* thr,
+                             long long* label, uint8_t* pseudo, msl_stream_t stream) {
+  TtaTable t;
+  if (!geo_ok(c, 1, 1, ho, wo) || !make_tta(entries, n, c, ho, wo, &t) || !thr || !(label || pseudo))
+    return MSL_ERR_ARG;
+  const int vec = wo % 4 == 0 && dword_aligned(pseudo);
+  MSL_DISPATCH_C(c, CM,
+                 MSL_LAUNCH((k_pseudo_classwise_tta<CM>), dim3(image_blocks(ho, wo)), dim3(256), 0,
+                            as_stream(stream), t, n, c, ho, wo, thr, label, pseudo, vec));
   MSL_CHECK_LAUNCH();
   return MSL_OK;
 }

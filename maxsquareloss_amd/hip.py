@@ -160,6 +160,11 @@ SIGNATURES = {
     "msl_predict_tta_max_entries": (c_int, []),
     "msl_predict_tta": (c_int, [c_p] + [c_int] * 4 + [c_p, c_p, c_p, c_p]),
     "msl_predict_tta_images": (c_int, [c_p] + [c_int] * 4 + [c_p, c_p, c_f] + [c_p] * 9),
+    "msl_confidence_hist": (c_int, [c_p, c_p] + [c_int] * 6 + [c_p, c_p]),
+    "msl_confidence_hist_tta": (c_int, [c_p] + [c_int] * 5 + [c_p, c_p]),
+    "msl_class_thresholds": (c_int, [c_p, c_int, c_int, c_d, c_f, c_p, c_p, c_p]),
+    "msl_pseudo_classwise": (c_int, [c_p, c_p] + [c_int] * 5 + [c_p, c_p, c_p, c_p]),
+    "msl_pseudo_classwise_tta": (c_int, [c_p] + [c_int] * 4 + [c_p, c_p, c_p, c_p]),
     "msl_image_metrics": (c_int, [c_p, c_p, c_int, c_d, c_p, c_int, c_p, c_p]),
     "msl_analysis_maps": (c_int, [c_p] * 5 + [c_int] * 3 + [c_p, c_ll] + [c_p] * 5),
     "msl_launch_guard_probe": (c_int, [c_int, c_p, c_p]),
@@ -173,9 +178,12 @@ ABI_VERSION = 3
 # r06 entry points an older build (MSL_LIB_PATH, a same-box A/B) may lack: the diagnostics probe and the masked
 # residual dgrad (ops.py falls back to the materialised residual gradient without it)
 # and the prediction-image entry points (ops.predict_images / ops.colorize raise without them), as do the
-# per-image analysis ones (ops.image_metrics / ops.analysis_maps)
+# per-image analysis ones (ops.image_metrics / ops.analysis_maps) and the class-threshold ones
+# (ops.confidence_hist / ops.class_thresholds / ops.pseudo_classwise)
 _DIAGNOSTIC = {"msl_launch_guard_probe", "msl_pconv_dgrad_resmask_sc", "msl_pconv_dgrad_resmask_f16",
-               "msl_predict_images", "msl_colorize", "msl_image_metrics", "msl_analysis_maps"}
+               "msl_predict_images", "msl_colorize", "msl_image_metrics", "msl_analysis_maps",
+               "msl_confidence_hist", "msl_confidence_hist_tta", "msl_class_thresholds", "msl_pseudo_classwise",
+               "msl_pseudo_classwise_tta"}
 _lib = None
 
 

@@ -1303,6 +1303,101 @@ def predict_tta_images(entries, out_hw, label=None, confusion=None, want=("color
     return out
 
 
+# --------------------------------------------------------------------------- class-balanced thresholds
+def _source_of(name, low, low_flip, entries):
+    """The source of a confidence / pseudo-label call: single scale (`low`, optional `low_flip`) or an entry
+    table (`entries`, as predict_tta).  Returns (entry point suffix, leading arguments, C, device, the
+    (hi, wi) of a single-scale call, the tensors to keep alive)."""
+    if entries is not None:
+        if low is not None or low_flip is not None:
+            raise hip.MSLError(f"{name}: give low (and low_flip) or entries, not both")
+        table, lows, c = _tta_table(entries, name)
+        return "_tta", (table, len(lows)), c, lows[0].device, (), lows
+    if low is None:
+        raise hip.MSLError(f"{name}: give low (and low_flip) or entries")
+    low = _check_act(low.detach(), name)
+    if low_flip is not None:
+        low_flip = _check_act(low_flip.detach(), name)
+        if low_flip.shape != low.shape:
+            raise hip.MSLError(f"{name}: low_flip must have low's shape")
+    return "", (low.data_ptr(), hip.ptr(low_flip)), low.shape[1], low.device, tuple(low.shape[2:]), (low, low_flip)
+
+
+def confidence_buffers(num_classes, bins, device):
+    """(hist int64 [C, bins], thr fp32 [C], kept int64 [C]) on the device: the zeroed histogram of
+    confidence_hist and the outputs of class_thresholds (the counts are uint64 in the library)."""
+    return (torch.zeros((int(num_classes), int(bins)), dtype=torch.int64, device=device),
+            torch.empty(int(num_classes), dtype=_f32, device=device),
+            torch.zeros(int(num_classes), dtype=torch.int64, device=device))
+
+
+def _check_hist(name, hist, c):
+    if (not hist.is_cuda or hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != c or
+            not hist.is_contiguous()):
+        raise hip.MSLError(f"{name}: hist must be a contiguous CUDA int64 tensor of shape ({c}, bins)")
+    return int(hist.shape[1])
+
+
+def confidence_hist(hist, out_hw, low=None, low_flip=None, entries=None):
+    """hist[class][bin] += 1 for every pixel of out_hw (msl_confidence_hist[_tta]): the class is predict_up's
+    (predict_tta's with `entries`), the bin min(bins - 1, int(top * bins)) of the probability behind
+    predict_images' "pseudo" map.  `hist`: int64 [C, bins] on the device, accumulated in place; bins a power
+    of two in [16, 1024] with C * bins <= 16384.  A NaN pixel is not counted."""
+    sfx, head, c, device, hw, keep = _source_of("confidence_hist", low, low_flip, entries)
+    bins = _check_hist("confidence_hist", hist, c)
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    name = "msl_confidence_hist" + sfx
+    hip.check(getattr(hip.load(), name)(*head, c, *hw, ho, wo, bins, hist.data_ptr(), hip.stream_ptr()), name)
+    return hist
+
+
+def class_thresholds(hist, portion, thr_max, thr=None, kept=None):
+    """One threshold per class from a confidence histogram (msl_class_thresholds): the largest bin edge that
+    still keeps `portion` of the class's pixels at or above it, capped at `thr_max`; an empty class gets
+    thr_max.  Writes `thr` (fp32 [C]) and `kept` (int64 [C]: the pixels at or above the threshold's bin), fresh
+    tensors when not given; nothing is read by the host.  Returns (thr, kept)."""
+    c = hist.shape[0] if hist.dim() == 2 else -1
+    bins = _check_hist("class_thresholds", hist, c)
+    if thr is None:
+        thr = torch.empty(c, dtype=_f32, device=hist.device)
+    if kept is None:
+        kept = torch.empty(c, dtype=torch.int64, device=hist.device)
+    for t, dt, what in ((thr, _f32, "thr"), (kept, torch.int64, "kept")):
+        if not t.is_cuda or t.dtype != dt or t.numel() != c or not t.is_contiguous():
+            raise hip.MSLError(f"class_thresholds: {what} must be a contiguous CUDA {dt} tensor with {c} elements")
+    hip.check(hip.load().msl_class_thresholds(hist.data_ptr(), c, bins, float(portion), float(thr_max),
+                                              thr.data_ptr(), kept.data_ptr(), hip.stream_ptr()),
+              "msl_class_thresholds")
+    return thr, kept
+
+
+def pseudo_classwise(thr, out_hw, low=None, low_flip=None, entries=None, label=None, pseudo=None,
+                     want=("label",)):
+    """The pseudo-label under one threshold per class (msl_pseudo_classwise[_tta]): the class where the
+    winning probability > thr[class], else ignored.  `thr`: fp32 [C] on the device, read by the kernel.
+    Writes `label` (int64 [ho*wo], -1 = ignored) and / or `pseudo` (uint8 (ho, wo), 255 = ignored): the
+    buffers given, or fresh ones for the names in `want`.  Returns (label, pseudo), None where not written."""
+    sfx, head, c, device, hw, keep = _source_of("pseudo_classwise", low, low_flip, entries)
+    ho, wo = int(out_hw[0]), int(out_hw[1])
+    if not thr.is_cuda or thr.dtype != _f32 or thr.numel() != c or not thr.is_contiguous():
+        raise hip.MSLError(f"pseudo_classwise: thr must be a contiguous CUDA float32 tensor with {c} elements")
+    if label is None and pseudo is None:
+        if "label" in want:
+            label = torch.empty(ho * wo, dtype=torch.int64, device=device)
+        if "pseudo" in want:
+            pseudo = torch.empty((ho, wo), dtype=torch.uint8, device=device)
+    for t, dt, what in ((label, torch.int64, "label"), (pseudo, torch.uint8, "pseudo")):
+        if t is not None and (not t.is_cuda or t.dtype != dt or t.numel() != ho * wo or not t.is_contiguous()):
+            raise hip.MSLError(f"pseudo_classwise: {what} must be a contiguous CUDA {dt} tensor with {ho * wo} "
+                               "elements")
+    if label is None and pseudo is None:
+        raise hip.MSLError("pseudo_classwise: nothing to compute (no label and no pseudo map)")
+    name = "msl_pseudo_classwise" + sfx
+    hip.check(getattr(hip.load(), name)(*head, c, *hw, ho, wo, thr.data_ptr(), hip.ptr(label), hip.ptr(pseudo),
+                                        hip.stream_ptr()), name)
+    return label, pseudo
+
+
 def colorize(mask, palette):
     """decode_labels on the device (msl_colorize): `mask` a CUDA int64 / int32 class map of any shape S,
     `palette` a CUDA uint8 [C, 3]; returns uint8 S + (3,), black where the value is outside [0, C)."""

@@ -30,6 +30,7 @@ import torch
 
 from .. import ops
 from ..utils.synthetic import init_weights
+from ..utils.thresholds import add_parse_check, load_class_thresholds
 from ..utils.train_helper import get_model
 from ..utils.images import SUMMARY_EVERY, OutputRequest, parse_save_kinds
 from ..utils.validate import SINGLE_SCALE, Validator, scales_arg, val_info
@@ -118,8 +119,12 @@ def output_request(args, out_size=None):
         directory, every = os.path.join(str(args.save_dir), "images"), SUMMARY_EVERY
     if directory is None:
         return None
+    values = getattr(args, "class_threshold_values", None)
+    if values is None and getattr(args, "class_thresholds", None) is not None:  # a namespace built by hand
+        values = load_class_thresholds(args.class_thresholds, args.num_classes)
     return OutputRequest(directory, getattr(args, "save_kinds", ("color",)), getattr(args, "threshold", 0.95),
-                         getattr(args, "data_loader_workers", 0), out_size=out_size, every=every)
+                         getattr(args, "data_loader_workers", 0), out_size=out_size, every=every,
+                         class_thresholds=values)
 
 
 def add_scales_arg(parser):
@@ -137,7 +142,19 @@ def add_save_args(parser):
       help="comma-separated: color,trainids,labelids,confidence,pseudo,input (default color)")
     if not any("--threshold" in act.option_strings for act in parser._actions):
         a("--threshold", type=float, default=0.95, help="the pseudo kind keeps a class where its probability > this")
+    a("--class_thresholds", type=str, default=None, metavar="FILE",
+      help="a class_thresholds.json of tools/pseudo_thresholds.py: the pseudo kind then keeps a class where its "
+           "probability > that class's own threshold (one more launch, msl_pseudo_classwise; not in the reference)")
+    add_parse_check(parser, read_class_thresholds)
     return parser
+
+
+def read_class_thresholds(ns):
+    """--class_thresholds against --num_classes, known only once both are parsed (a parser error through
+    utils/thresholds.py add_parse_check); the values go to ns.class_threshold_values."""
+    ns.class_threshold_values = None
+    if ns.class_thresholds is not None:
+        ns.class_threshold_values = load_class_thresholds(ns.class_thresholds, ns.num_classes)
 
 
 def build_parser():

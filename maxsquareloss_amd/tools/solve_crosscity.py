@@ -10,7 +10,8 @@ CrossCityTrainer is UDATrainer with other data: --pair, --graph, data-parallel e
     2048x1024 JPEGs are Huffman-decoded on the decoding threads and finished on the device (--jpeg_decode);
   - main() validates on the city's test split and on the source's val split (validate_source) before it
     trains, and validates the source again after every epoch; the source numbers are logged only;
-  - one run is --epoch_num epochs (no rounds), --lambda_target 0.1 and --threshold 0.98 by default.
+  - one run is --epoch_num epochs (no rounds), --lambda_target 0.1 and --threshold 0.98 by default; with
+    --target_mode hard --threshold_mode class the per-class thresholds are regenerated before every epoch.
 Without paths the source and target items are synthetic, as in every trainer here; validate_source then runs
 on --val_images synthetic items of the source size.
 """
@@ -97,6 +98,10 @@ class CrossCityTrainer(UDATrainer):
         self.train()
 
     def train_one_epoch(self, epoch=0):
+        # this trainer has no rounds: with --threshold_mode class the per-class thresholds are regenerated at
+        # the top of every epoch (UDATrainer.generate_thresholds; nothing with `fixed`)
+        if getattr(self, "threshold_pass", None) is not None:
+            self.generate_thresholds(f"epoch {self.current_epoch}")
         super().train_one_epoch(epoch)
         self.validate_source()  # solve_crosscity.py:273-274
 

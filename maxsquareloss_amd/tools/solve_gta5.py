@@ -17,6 +17,9 @@ same sums, added inside the weight-gradient GEMMs instead of by a second pass.
 
 The losses run fused from the low-resolution logits (utils/loss.py), so the
 two softmax tensors of the reference (:182-183) are never materialised.
+With --target_mode hard --threshold_mode class every round opens with a statistics pass over target
+images (generate_thresholds; utils/thresholds.py) that gives each class its own pseudo-label threshold -
+the reference's "# generate threshold", which there assigns the constant.
 Style transfer inside the loop is tools/ADAIN.py, which subclasses this trainer
 (DESIGN.md §3.14).
 
@@ -35,10 +38,12 @@ import torch
 from .. import ops
 from ..datasets import build_loader
 from ..hip import MSLError
-from ..utils.loss import (IW_MaxSquareloss, IWsoftCrossEntropy, MaxSquareloss, multi_level_guidance_ce,
-                          pseudo_label_ce, softCrossEntropy)
+from ..utils.checkpoint import load_checkpoint, save_checkpoint
+from ..utils.loss import (IW_MaxSquareloss, IWsoftCrossEntropy, MaxSquareloss, PseudoLabelCEClasswise,
+                          multi_level_guidance_ce, pseudo_label_ce, softCrossEntropy)
 from ..utils.graph import GraphedStep
 from ..utils.synthetic import SyntheticDomain
+from ..utils.thresholds import ThresholdPass, add_parse_check, check_pass_flags, first_items, pass_loader
 from .train_source import Trainer, add_train_args, dataset_paths, init_args, str2bool
 
 
@@ -69,6 +74,21 @@ class UDATrainer(Trainer):
             self.target_loss = lambda pred: pseudo_label_ce(pred, self.threshold)
         else:
             raise NotImplementedError(f"unknown target_mode {mode!r}")
+        # --threshold_mode class: one threshold per class, regenerated at the top of every round
+        # (generate_thresholds); the loss reads them from this device tensor, allocated once
+        self.threshold_mode = getattr(self.args, "threshold_mode", "fixed")
+        self.threshold_pass = self.class_thresholds = None
+        if self.threshold_mode == "class":
+            if mode != "hard":
+                raise MSLError("--threshold_mode class needs --target_mode hard")
+            self.threshold_pass = ThresholdPass(self.model, self.args.num_classes, self.args.threshold_bins,
+                                                self.device, portion=self.args.pseudo_portion,
+                                                thr_max=self.args.threshold)
+            self.class_thresholds = self.threshold_pass.thr
+            self._classwise_ce = PseudoLabelCEClasswise()
+            self.target_loss = lambda pred: self._classwise_ce(pred, self.class_thresholds)
+        elif self.threshold_mode != "fixed":
+            raise MSLError(f"unknown threshold_mode {self.threshold_mode!r}")
         self.current_round = self.args.init_round
         self.round_num = self.args.round_num
         self.threshold = self.args.threshold
@@ -339,8 +359,55 @@ class UDATrainer(Trainer):
         self.optimizer.zero_grad()
         for _ in range(self.current_round, self.round_num):
             self.epoch_num = self.current_epoch + (self.current_round + 1) * self.args.epoch_each_round
+            if getattr(self, "threshold_pass", None) is not None:
+                self.generate_thresholds()  # the reference's "# generate threshold" (its train_round())
             self.train()
             self.current_round += 1
+
+    # ---------------------------------------------------------------- class-balanced thresholds
+    def threshold_items(self):
+        """The first --threshold_images items (0: all) of the target train list for the statistics pass,
+        with the val transform - resize only, no mirror, no crop - through a loader of their own: the
+        training loader's random stream and epoch counter do not move (utils/thresholds.py pass_loader).
+        Synthetic: the target domain's items in order, rank 0's on every rank (a rank's own training items
+        differ by its seed; the pass must count the same images everywhere)."""
+        n = int(getattr(self.args, "threshold_images", 500))
+        if not self.file_backed:
+            d = self.target_dataloader
+            data = d if d.rank == 0 else SyntheticDomain(d.h, d.w, d.c, d.n, rank=0, offset=d.offset)
+            return (data[i] for i in range(min(n, len(data)) if n > 0 else len(data)))
+        if getattr(self, "_threshold_loader", None) is None:
+            self._threshold_loader = pass_loader(self.target_dataloader, getattr(self.args, "seed", 12345))
+        return first_items(self._threshold_loader, n)
+
+    def generate_thresholds(self, when=None):
+        """With --threshold_mode class: the statistics pass (utils/thresholds.py) over threshold_items() with
+        the model in eval mode, one threshold per class into self.class_thresholds (in place: a captured step
+        reads the new values), and the per-class table in the log.  Every rank runs the same pass over the
+        same items - the file list in order, or rank 0's synthetic items - so the thresholds are the same
+        everywhere without an exchange.  `when` titles the table (default: the round).  `fixed`: nothing."""
+        if self.threshold_pass is None:
+            return None
+        self.threshold_pass.run(self.threshold_items())
+        return self.threshold_pass.log(self.logger, f"{when or f'round {self.current_round}'}: class thresholds")
+
+    def save_checkpoint(self, filename=None):
+        if self.class_thresholds is None:
+            return super().save_checkpoint(filename)
+        if self.rank != 0 or not self.args.save_dir:
+            return
+        save_checkpoint(os.path.join(self.args.save_dir, filename), self.model, self.optimizer,
+                        self.current_epoch + 1, self.current_iter, self.best_MIou,
+                        class_thresholds=self.class_thresholds)
+
+    def load_checkpoint(self, filename):
+        got = load_checkpoint(filename, self.model, self.optimizer, map_location=self.device)
+        if got:
+            self.current_epoch = got["epoch"]
+            self.current_iter = got["iteration"]
+            self.best_MIou = got["best_MIou"]
+            if self.class_thresholds is not None and "class_thresholds" in got:
+                self.class_thresholds.copy_(got["class_thresholds"])
 
     def train(self):
         for epoch in range(self.current_epoch, self.epoch_num):
@@ -390,7 +457,20 @@ def add_UDA_train_args(arg_parser, source_datasets=("gta5", "synthia")):
     a("--lambda_target", type=float, default=1)
     a("--gamma", type=float, default=0)
     a("--IW_ratio", type=float, default=0.2)
-    a("--threshold", type=float, default=0.95)
+    a("--threshold", type=float, default=0.95,
+      help="the confidence a hard pseudo-label needs; with --threshold_mode class the cap of the per-class "
+           "thresholds.  --multi's guidance label always uses this one value")
+    a("--threshold_mode", type=str, default="fixed", choices=["fixed", "class"],
+      help="class: --target_mode hard with one threshold per class, regenerated at the top of every round from "
+           "that class's own confidence distribution over the target images - the largest value that still keeps "
+           "--pseudo_portion of the class's pixels, at most --threshold (CBST / BDL; not in the reference, whose "
+           "rounds assign the constant).  --multi's guidance label keeps the scalar --threshold")
+    a("--pseudo_portion", type=float, default=0.5,
+      help="--threshold_mode class: the share of each class's pixels its threshold keeps at least")
+    a("--threshold_bins", type=int, default=512,
+      help="--threshold_mode class: bins of the confidence histogram, a power of two in [16, 1024]")
+    a("--threshold_images", type=int, default=500,
+      help="--threshold_mode class: target train images of the statistics pass (0 = the whole list)")
     a("--target_solo_epoch", type=int, default=0)
     a("--pair", type=str2bool, default=True,
       help="run the source and target images of an iteration as one image pair (per-image BatchNorm "
@@ -404,7 +484,19 @@ def add_UDA_train_args(arg_parser, source_datasets=("gta5", "synthia")):
     a("--dp_exchange", type=str2bool, default=False,
       help="run the data-parallel gradient exchange (RCCL process group + GradReducer) even at one rank, "
            "where the all-reduce is the identity: the multi-GPU code path on one GPU (not in the reference)")
+    add_parse_check(arg_parser, check_threshold_flags)
     return arg_parser
+
+
+def check_threshold_flags(ns):
+    """What only the parsed flags together can tell (utils/thresholds.py add_parse_check: a parser error)."""
+    if ns.threshold_mode != "class":
+        return
+    if ns.target_mode != "hard":
+        raise MSLError(f"--threshold_mode class needs --target_mode hard, not {ns.target_mode}")
+    check_pass_flags(ns)
+    if ns.threshold_images < 0:
+        raise MSLError("--threshold_images must not be negative")
 
 
 def build_parser():

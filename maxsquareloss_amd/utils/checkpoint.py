@@ -17,14 +17,19 @@ import torch
 log = logging.getLogger(__name__)
 
 
-def save_checkpoint(path, model, optimizer, epoch, iteration, best_MIou, module_prefix=False):
+def save_checkpoint(path, model, optimizer, epoch, iteration, best_MIou, module_prefix=False,
+                    class_thresholds=None):
     """Write the reference's checkpoint dict to `path`.  module_prefix=True writes the keys as the
-    reference's nn.DataParallel(model, device_ids=[0]) wrapper names them ('module.conv1.weight')."""
+    reference's nn.DataParallel(model, device_ids=[0]) wrapper names them ('module.conv1.weight').
+    `class_thresholds` (--threshold_mode class: the fp32 [C] tensor of the round) adds a key of that name;
+    without it the file is what it always was."""
     sd = model.state_dict()
     if module_prefix:
         sd = {"module." + k: v for k, v in sd.items()}
     state = {"epoch": epoch, "iteration": iteration, "state_dict": sd,
              "optimizer": optimizer.state_dict(), "best_MIou": best_MIou}
+    if class_thresholds is not None:
+        state["class_thresholds"] = class_thresholds.detach().to("cpu", torch.float32).clone()
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -33,7 +38,8 @@ def save_checkpoint(path, model, optimizer, epoch, iteration, best_MIou, module_
 
 def load_checkpoint(path, model, optimizer=None, map_location=None):
     """Restore `model` (and `optimizer`) from `path`.  Returns None when the file does not exist,
-    {} when it holds weights only, else {'epoch', 'iteration', 'best_MIou'}."""
+    {} when it holds weights only, else {'epoch', 'iteration', 'best_MIou'} - and 'class_thresholds' when
+    the file has that key."""
     try:
         ckpt = torch.load(path, map_location=map_location, weights_only=True)
     except OSError:
@@ -46,4 +52,7 @@ def load_checkpoint(path, model, optimizer=None, map_location=None):
         return {}
     if optimizer is not None:
         optimizer.load_state_dict(ckpt["optimizer"])
-    return {"epoch": ckpt["epoch"], "iteration": ckpt["iteration"], "best_MIou": ckpt["best_MIou"]}
+    got = {"epoch": ckpt["epoch"], "iteration": ckpt["iteration"], "best_MIou": ckpt["best_MIou"]}
+    if "class_thresholds" in ckpt:
+        got["class_thresholds"] = ckpt["class_thresholds"]
+    return got

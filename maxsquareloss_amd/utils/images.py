@@ -57,9 +57,13 @@ class OutputRequest:
     `workers`, optionally `out_size` (W, H) to upsample to instead of the input size (unlabelled data
     only), and which items: every one, the first `first` of them, or every `every`-th and the last."""
 
-    def __init__(self, directory, kinds=("color",), threshold=0.95, workers=0, out_size=None, first=None, every=None):
+    def __init__(self, directory, kinds=("color",), threshold=0.95, workers=0, out_size=None, first=None, every=None,
+                 class_thresholds=None):
+        """`class_thresholds`: one threshold per class (--class_thresholds FILE); the pseudo kind then keeps a
+        class where its probability > that class's own value instead of `threshold`."""
         self.directory, self.kinds = str(directory), parse_save_kinds(",".join(kinds))
         self.threshold, self.workers = float(threshold), int(workers)
+        self.class_thresholds = None if class_thresholds is None else tuple(float(t) for t in class_thresholds)
         self.out_size = None if out_size is None else (int(out_size[0]), int(out_size[1]))
         self.first, self.every = first, every
 

@@ -7,6 +7,7 @@ from the logits behind `pred` (the low-res ASPP output when `pred` came from
 this package's DeeplabMulti), with softmax, upsampling and the loss fused into
 one forward and one backward kernel pair.
 """
+import torch
 import torch.nn as nn
 
 from .. import ops
@@ -138,3 +139,32 @@ def pseudo_label_ce(pred, threshold):
     passes (quirk Q8)."""
     low, hw = _fused_source(pred)
     return ops.hard_ce_up(low, hw, threshold)
+
+
+class PseudoLabelCEClasswise(nn.Module):
+    """The `hard` target mode with one threshold per class (--threshold_mode class): label = argmax
+    softmax(pred) where its maximum > thr_dev[that class], else ignored, written as an int64 map by one
+    launch (ops.pseudo_classwise) into a buffer this object owns; then the fused CE of the low-resolution
+    logits with that map (ops.ce_up).  One launch more than pseudo_label_ce, no other loss kernel.
+    `thr_dev` is a device fp32 [C] tensor the launch reads: a captured step follows new values.
+    The CE's backward reads the buffer: run a call's backward before the same object's next forward."""
+
+    def __init__(self):
+        super().__init__()
+        self.labels = None  # int64 [ho*wo], allocated on the first call and whenever the size changes
+
+    def forward(self, pred, thr_dev):
+        low, hw = _fused_source(pred)
+        n = int(hw[0]) * int(hw[1])
+        if self.labels is None or self.labels.numel() != n or self.labels.device != low.device:
+            self.labels = torch.empty(n, dtype=torch.int64, device=low.device)
+        ops.pseudo_classwise(thr_dev, hw, low.detach(), label=self.labels)
+        return ops.ce_up(low, self.labels, hw)
+
+
+def pseudo_label_ce_classwise(pred, thr_dev):
+    """PseudoLabelCEClasswise as a function, with a label map of its own per call: the CE's backward reads the
+    map its forward saved, so two losses formed before either backward must not share one.  A trainer keeps one
+    PseudoLabelCEClasswise instead (one forward, then its backward, per step: a static buffer for a captured
+    step)."""
+    return PseudoLabelCEClasswise()(pred, thr_dev)

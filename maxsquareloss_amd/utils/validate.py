@@ -105,7 +105,32 @@ def predict_image(model, ev, x, y, hw, flip, images=None, thr=0.95, scales=SINGL
     """One image into ev's matrix: x (1,3,H,W) fp32, y int64 (H*W labels), both on the device; hw is
     the size the prediction is upsampled to.  `images` (ops.image_buffers) also receives the prediction
     as uint8 maps, in the same launch; with them y may be None (an unlabelled image: no matrix).
-    `scales` other than (1.0,): the multi-scale fusion of the module text."""
+    `scales` other than (1.0,): the multi-scale fusion of the module text.  `thr` as a device fp32 [C]
+    tensor (--class_thresholds): the "pseudo" map comes from a launch of its own under one threshold per
+    class (ops.pseudo_classwise), every other map and the matrix from the launch they always came from."""
+    if torch.is_tensor(thr):
+        pseudo = images.get("pseudo") if images else None
+        if pseudo is None:
+            thr = 0.95  # no map reads it
+        else:
+            rest = {k: v for k, v in images.items() if k != "pseudo"}
+            entries = low = low_f = None
+            if tuple(scales) != SINGLE_SCALE:
+                entries = tta_entries(model, x, scales, flip)
+            elif flip:
+                (low, _), (low_f, _) = model.predict_low(x, flip=True)
+            else:
+                low = model.predict_low(x)[0]
+            if y is not None and entries is not None:
+                ev.add_batch_tta(y, entries, hw, images=rest or None)
+            elif y is not None:
+                ev.add_batch_low(y, low, hw, low_f, images=rest or None)
+            elif rest and entries is not None:
+                ops.predict_tta_images(entries, hw, out=rest)
+            elif rest:
+                ops.predict_images(low, hw, low_f, out=rest)
+            ops.pseudo_classwise(thr, hw, low, low_f, entries, pseudo=pseudo)
+            return
     if tuple(scales) != SINGLE_SCALE:
         if y is None and not images:
             if images is None:
@@ -236,6 +261,12 @@ class Validator:
         if outputs is None and not self.labelled:
             raise MSLError("Validator: unlabelled data and no output request - nothing to compute")
         self.Eval = Eval(num_classes)
+        self._class_thr = None  # --class_thresholds: the device fp32 [C] tensor the pseudo kind's launch reads
+        if outputs is not None and getattr(outputs, "class_thresholds", None) is not None:
+            if len(outputs.class_thresholds) != int(num_classes):
+                raise MSLError(f"--class_thresholds holds {len(outputs.class_thresholds)} classes, the model has "
+                               f"{num_classes}")
+            self._class_thr = torch.tensor(outputs.class_thresholds, dtype=torch.float32, device=device)
         if data is None:
             data = SyntheticDomain(self.hw[0], self.hw[1], num_classes, images, rank=rank, offset=VAL_OFFSET)
         self.data = data
@@ -278,12 +309,14 @@ class Validator:
                     if y is None and not save:
                         continue
                     maps, thr = (req.maps, req.threshold) if save else (None, 0.95)
+                    if save and self._class_thr is not None and "pseudo" in maps:
+                        thr = self._class_thr
                     if self.use_graph:
                         key = self.flip if size == self.hw else (self.flip, size)
                         if self.scales != SINGLE_SCALE:
                             key = (key, "scales", self.scales)
                         if save or y is None:  # another body: its own capture and static output buffers
-                            key = (key, hw, maps, thr, y is None)
+                            key = (key, hw, maps, "class" if torch.is_tensor(thr) else thr, y is None)
                         if key not in self._graphed:
                             self._graphed[key] = GraphedPredict(self.model, self.Eval, hw, self.flip, self.device,
                                                                 maps, thr, self.scales)
